@@ -102,6 +102,17 @@ def test_bench_launches_n_ranks_itself():
     assert ln["bundle_broadcast_ok"] is True
 
 
+def test_bench_steps_and_options(tmp_path):
+    """--steps sets the number of steps the line reports with its ms_per_step;
+    --full and --dump-outputs are accepted (the launcher flow itself measures
+    nothing and writes nothing)."""
+    r, lines = _run_bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--full",
+                           "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1, r.stdout
+    assert lines[0]["steps"] == 4 and lines[0]["warmup"] == 1 and lines[0]["ms_per_step"] > 0
+
+
 def test_bench_refuses_world_mismatch():
     """Under an external launcher, WORLD_SIZE must equal --gpus."""
     r, lines = _run_bench(["--gpus", "2"], extra_env=dict(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))

@@ -43,7 +43,7 @@ if [ "${NTT:-1}" = 1 ]; then
 fi
 for rep in $(seq 1 ${BENCH:-2}); do
   for v in "$@"; do
-    run_env $v timeout -k 10 300 python bench.py --no-cpu-baseline --no-extras > ${O}_bench_${v}_$rep.log 2>&1 || { echo "bench $v failed"; tail -20 ${O}_bench_${v}_$rep.log; exit 1; }
+    run_env $v timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extras > ${O}_bench_${v}_$rep.log 2>&1 || { echo "bench $v failed"; tail -20 ${O}_bench_${v}_$rep.log; exit 1; }
     echo "$v bench $rep: $(summ ${O}_bench_${v}_$rep.log)"
   done
 done
@@ -55,7 +55,7 @@ if [ "${RESNET:-0}" = 1 ]; then
 fi
 if [ "${KPROF:-0}" = 1 ]; then
   for v in "$@"; do
-    run_env $v timeout -k 10 300 rocprofv3 --kernel-trace --stats -d ${O}_kprof -o $v --output-format csv -- python bench.py --no-cpu-baseline --no-extras --steps 5 --warmup 2 > ${O}_kprof_$v.log 2>&1 || { echo "kprof $v failed"; tail -20 ${O}_kprof_$v.log; exit 1; }
+    run_env $v timeout -k 10 300 rocprofv3 --kernel-trace --stats -d ${O}_kprof -o $v --output-format csv -- python bench.py --full --no-cpu-baseline --no-extras --steps 5 --warmup 2 > ${O}_kprof_$v.log 2>&1 || { echo "kprof $v failed"; tail -20 ${O}_kprof_$v.log; exit 1; }
     f=$(find ${O}_kprof -name "${v}_kernel_stats.csv" | head -1)
     python tools/rocpd_stats.py --csv "$f" 10 | sed "s/^/$v  /"
   done

@@ -15,9 +15,9 @@ for r in $(seq 1 ${REPS:-2}); do
     o=gpurun_out/b1ab_${TAG}_${v}_$r.log
     if [ "$MODE" = lib ]; then
       lib=orion_amd/liborion_hip.so; [ "$v" != product ] && lib=orion_amd/_build/liborion_hip_$v.so
-      ORION_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --steps 3 --warmup 1 > $o 2>&1 || { tail -20 $o; exit 1; }
+      ORION_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $o 2>&1 || { tail -20 $o; exit 1; }
     else
-      env "$VAR=$v" timeout -k 10 300 python bench.py --no-cpu-baseline --steps 3 --warmup 1 > $o 2>&1 || { tail -20 $o; exit 1; }
+      env "$VAR=$v" timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $o 2>&1 || { tail -20 $o; exit 1; }
     fi
     echo "$v $r: $(tail -1 $o | python -c 'import json,sys; d=json.loads(sys.stdin.read()); b=d["batch1"]; print("batch1 graph", b["ms_per_image"], "stream", b["stream_ms_per_image"], "ms; B=64", d["value"], "img/s", d["kernel_ms_per_step"])')"
   done

@@ -3,7 +3,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${1:-r01}
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-extras"
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-extras"  # (--full: the "single" and "solo" windows)
 rm -f gpurun_out/prof_$TAG/ntt_log_*.txt; mkdir -p gpurun_out/prof_$TAG
 ORION_NTT_LOG=gpurun_out/prof_$TAG/ntt_log_kt.txt timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o kt --output-format csv -- python bench.py $ARGS > gpurun_out/prof_${TAG}_kt.log 2>&1 || { echo "kt failed"; tail -20 gpurun_out/prof_${TAG}_kt.log; exit 1; }
 echo "kt ok"
