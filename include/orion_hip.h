@@ -258,6 +258,34 @@ int EncodeBatch(float *values, int lenPerImage, int batch, int level, unsigned l
 int GetCiphertextBatch(int ct);
 int GetPlaintextBatch(int pt);
 double GetCiphertextScaleF(int ct);                       /* exact-ish scale (long double -> double) */
+/* Batches from ciphertexts that already live on the device, and back: a
+ * server stacks separately encrypted inputs (same key), runs the op stream
+ * once at batch B, and slices each client's output off the result.
+ *
+ * OrionHipStackCiphertexts: one new batch ciphertext holding the images of
+ * cts[0], cts[1], ... in that order (B = the sum of their batches; a source
+ * may itself be a batch, and the same handle may appear more than once).
+ * OrionHipSliceCiphertext: one new batch ciphertext holding the images
+ * first .. first+count-1 of ct.  Both copy with one gather kernel launch per
+ * 64 output images, asynchronously on the calling thread's context's stream
+ * (like CloneCiphertext); the sources are only read and stay alive, and the
+ * result shares no buffer with them (a copy-on-write source is read, not
+ * unshared).  The result has the sources' level and scale and belongs to the
+ * calling thread's context; a source of another context is read like any
+ * other op's foreign operand (this stream is ordered after its producer, and
+ * its owner may delete it afterwards).
+ *
+ * All sources must have the same level and bit-equal (long double) scales --
+ * ciphertexts produced by the same op stream, or encrypted at the same scale,
+ * do; the library does not rescale or drop moduli on the caller's behalf.
+ * Otherwise the call returns -1 and the error names the two handles and the
+ * two values.  -1 and an error also for n < 1, a null cts, an unknown handle,
+ * count < 1, first < 0, first + count larger than ct's batch, and a poisoned
+ * source (its poison message).  A failed call allocates no handle.  A pending
+ * deferred rotation runs first.  Neither call is allowed inside a graph
+ * capture (a graph would pin one request's source buffers). */
+int OrionHipStackCiphertexts(const int *cts, int n);
+int OrionHipSliceCiphertext(int ct, int first, int count);
 
 /* GPU encoder with device-resident slots (e.g. a torch tensor's data_ptr):
  * dvalues [batch][lenPerImage] float32; DecodeDevice writes the real parts of

@@ -168,6 +168,8 @@ SIGNATURES = {
     "GetCiphertextBatch": ([c_int], c_int),
     "GetPlaintextBatch": ([c_int], c_int),
     "GetCiphertextScaleF": ([c_int], c_double),
+    "OrionHipStackCiphertexts": ([P(c_int), c_int], c_int),
+    "OrionHipSliceCiphertext": ([c_int, c_int, c_int], c_int),
     "ImportCiphertext": ([P(c_ulong), c_int, c_int, c_double], c_int),
     "ExportCiphertext": ([c_int, P(c_ulong), c_ulong], c_int),
     "ImportPlaintext": ([P(c_ulong), c_int, c_int, c_double], c_int),
@@ -203,6 +205,11 @@ LATTIGO_SYMBOLS = [n for n in SIGNATURES if not n.startswith("OrionHip") and n n
     "ExportSecretKey", "ExportPublicKey", "ExportRelinKey",
     "ExportGaloisKey", "GetGaloisKeyLevel", "ExportLinearTransformDiagonal", "GetLinearTransformN1", "GaloisElement",
     "KeyBundleBytes", "ExportKeyBundle", "ImportKeyBundle", "ModDropCiphertext", "GetPolyDepth")]
+
+
+# output images one launch of the gather kernel behind OrionHipStackCiphertexts /
+# OrionHipSliceCiphertext covers (csrc/common.h ORION_MAXGATHER); more take more launches
+STACK_TABLE_SIZE = 64
 
 
 def _hip_runtimes():
@@ -433,6 +440,17 @@ class HipLibrary:
         B, _, nl, _ = arr.shape
         h = self.lib.ImportCiphertext(arr.ctypes.data_as(P(c_ulong)), B, nl - 1, float(scale))
         return self._chk(h, "ImportCiphertext")
+
+    def stack_ciphertexts(self, handles):
+        """One new batch ciphertext holding the images of `handles`, in order
+        (OrionHipStackCiphertexts): same level and scale required; the sources
+        stay alive.  Asynchronous on the calling thread's context's stream."""
+        return self.OrionHipStackCiphertexts([int(h) for h in handles])
+
+    def slice_ciphertext(self, ct, first, count=1):
+        """One new batch ciphertext holding images first .. first+count-1 of ct
+        (OrionHipSliceCiphertext); ct stays alive."""
+        return self.OrionHipSliceCiphertext(int(ct), int(first), int(count))
 
     # Device-pointer calls run asynchronously on the library stream, which
     # torch does not know about: order them against the tensor's stream both

@@ -37,6 +37,8 @@ int orion_launch_ew(int op, const LimbSet& o, const LimbSet& a, const LimbSet& b
                     const DeviceTables* tb, int N, hipStream_t st);
 int orion_launch_tensor(const LimbSet& d, const LimbSet& a, const LimbSet& b, const DeviceTables* tb, int N,
                         hipStream_t st);
+int orion_launch_gather(u64* dst, long long d_comp, long long d_limb, int nimg, int nlimb, const GatherTable& T,
+                        int N, hipStream_t st);
 int orion_launch_basis_ext(const LimbSet& out, const LimbSet& in, const BasisExtTable* T, const DeviceTables* tb,
                            int N, hipStream_t st);
 int orion_launch_modup_all(const LimbSet& D, const LimbSet& in, const BasisExtTable* Ts, int beta, int K,
@@ -2243,6 +2245,32 @@ struct Context {
     copy(lsq(c.poly, 0, 2, a.level), lsq(a.poly, 0, 2, a.level));
     return c;
   }
+  // image i of dst (its limbs 0..level) = the image src[i] points at, one
+  // launch per ORION_MAXGATHER images (StackCiphertexts / SliceCiphertext);
+  // bytes: 16 N per limb-image, read + write
+  void gather(Ciphertext& dst, const std::vector<GatherSrc>& src) {
+    const int nl = dst.level + 1;
+    const Poly& D = dst.poly;
+    if ((int)src.size() != D.B || D.nlimb < nl) throw std::runtime_error("gather: destination shape mismatch");
+    for (int b0 = 0; b0 < D.B; b0 += ORION_MAXGATHER) {
+      const int n = std::min(ORION_MAXGATHER, D.B - b0);
+      GatherTable T;
+      memset(&T, 0, sizeof(T));
+      for (int i = 0; i < n; ++i) T.src[i] = src[b0 + i];
+      Scope sc(this, P_EW, 16.0 * N * 2 * nl * n);
+      if (orion_launch_gather(D.ptr() + (long long)b0 * D.batch_stride(), D.comp_stride(), D.limb_stride(), n, nl, T,
+                              N, stream))
+        throw std::runtime_error("gather launch failed");
+    }
+  }
+  // the images [first, first + count) of a, as gather sources
+  static void gather_sources(const Ciphertext& a, int first, int count, std::vector<GatherSrc>& out) {
+    const Poly& P = a.poly;
+    if (!P.ptr() || P.ncomp < 2 || P.nlimb < a.level + 1 || first < 0 || count < 0 || first + count > P.B)
+      throw std::runtime_error("gather: source shape mismatch");
+    for (int b = first; b < first + count; ++b)
+      out.push_back(GatherSrc{P.ptr() + (long long)b * P.batch_stride(), P.comp_stride(), P.limb_stride()});
+  }
 
   void rescale_inplace(Ciphertext& ct) {
     const int l = ct.level;
@@ -3994,6 +4022,63 @@ int CloneCiphertext(int id) {
   API_BEGIN
   Context& c = ctx();
   return c.cts.add(c.clone(c.cts.get(id)));
+  API_END(-1)
+}
+static std::string scale_str(long double s) {
+  char b[64];
+  snprintf(b, sizeof(b), "%.21Lg", s);
+  return b;
+}
+int OrionHipStackCiphertexts(const int* ids, int n) {
+  API_BEGIN
+  Context& c = ctx();
+  if (n < 1) throw std::runtime_error("cannot stack " + std::to_string(n) + " ciphertexts: at least one is needed");
+  if (!ids) throw std::runtime_error("null handle list");
+  // every source is looked up (and checked) before anything is allocated; a
+  // source of another context orders this stream after its producer (cts.get)
+  std::vector<GatherSrc> src;
+  std::vector<std::shared_ptr<Buffer>> keep;  // the sources' buffers, until the launches are queued
+  int level = 0;
+  long double scale = 0;
+  for (int i = 0; i < n; ++i) {
+    const Ciphertext& a = c.cts.get(ids[i]);
+    if (i == 0) {
+      level = a.level, scale = a.scale;
+    } else if (a.level != level) {
+      throw std::runtime_error("cannot stack ciphertexts " + std::to_string(ids[0]) + " (level " +
+                               std::to_string(level) + ") and " + std::to_string(ids[i]) + " (level " +
+                               std::to_string(a.level) + "): the levels differ");
+    } else if (a.scale != scale) {
+      throw std::runtime_error("cannot stack ciphertexts " + std::to_string(ids[0]) + " (scale " + scale_str(scale) +
+                               ") and " + std::to_string(ids[i]) + " (scale " + scale_str(a.scale) +
+                               "): the scales differ");
+    }
+    if (src.size() + (size_t)a.poly.B > (size_t)0x7fffffff) throw std::runtime_error("stacked batch too large");
+    Context::gather_sources(a, 0, a.poly.B, src);
+    keep.push_back(a.poly.buf);
+  }
+  Ciphertext out = c.new_ct(level, (int)src.size(), scale);
+  c.gather(out, src);
+  return c.cts.add(std::move(out));
+  API_END(-1)
+}
+int OrionHipSliceCiphertext(int id, int first, int count) {
+  API_BEGIN
+  Context& c = ctx();
+  const Ciphertext& a = c.cts.get(id);
+  const int B = a.poly.B;
+  if (count < 1) throw std::runtime_error("slice of " + std::to_string(count) + " images: at least one is needed");
+  if (first < 0) throw std::runtime_error("slice starts at image " + std::to_string(first) + ": must not be negative");
+  if ((long long)first + count > B)
+    throw std::runtime_error("slice of images " + std::to_string(first) + ".." +
+                             std::to_string((long long)first + count - 1) + " of ciphertext " + std::to_string(id) +
+                             ", whose batch is " + std::to_string(B));
+  std::vector<GatherSrc> src;
+  std::shared_ptr<Buffer> keep = a.poly.buf;
+  Context::gather_sources(a, first, count, src);
+  Ciphertext out = c.new_ct(a.level, count, a.scale);
+  c.gather(out, src);
+  return c.cts.add(std::move(out));
   API_END(-1)
 }
 

@@ -251,6 +251,20 @@ struct MacGroups {  // ks_mac_kernel: group g uses key[g], made for level klvl[g
   int fwd_rows;
 };
 
+// gather of whole images into a batch ciphertext (gather_images_kernel:
+// StackCiphertexts / SliceCiphertext): output image i of a launch is read from
+// src[i], limb plane (c, l) at p + c*comp_stride + l*limb_stride (the source's
+// own Poly strides: its batch and allocated limbs may differ per image).  The
+// table travels by value in the kernel arguments (64 x 24 B = 1.5 KB)
+#define ORION_MAXGATHER 64
+struct GatherSrc {
+  const u64* p;
+  long long comp_stride, limb_stride;
+};
+struct GatherTable {
+  GatherSrc src[ORION_MAXGATHER];
+};
+
 // BSGS linear transform plan (device-resident, one per LinTrans): giants in
 // evaluation order, baby slots in the order of LinTrans::babies
 #define LT_MAXB 16   // baby rotations held in registers by one lt_bsgs launch

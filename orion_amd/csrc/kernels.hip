@@ -158,6 +158,34 @@ __global__ void __launch_bounds__(256) ew_kernel(LimbSet o, LimbSet a, LimbSet b
   *po = z;
 }
 
+// whole images gathered into a batch ciphertext: image i of the launch
+// (i < ORION_MAXGATHER) is copied from T.src[i] to dst + i*N, limb planes
+// (c, l), c < 2, l < nlimb, dst plane (c, l) at c*d_comp + l*d_limb.
+// Grid: x covers the N coefficients (kGatherU 16-B accesses per thread, all
+// loads issued before the first store; N is a multiple of a workgroup's
+// share, so there is no tail), y = image (neighbouring workgroups write
+// neighbouring memory), z = plane c*nlimb + l.
+constexpr int kGatherU = 4;
+__global__ void __launch_bounds__(256) gather_images_kernel(u64* __restrict__ dst, long long d_comp, long long d_limb,
+                                                            int nlimb, GatherTable T, int N) {
+  const int i = blockIdx.y;
+  const int pl = blockIdx.z;
+  const int c = pl >= nlimb ? 1 : 0;
+  const int l = pl - c * nlimb;
+  const GatherSrc s = T.src[i];  // wave-uniform: scalar loads from the kernel arguments
+  // 16-byte accesses: every plane base is 16-byte aligned -- pool buffers are
+  // hipMalloc allocations (256-byte aligned) and every offset (component,
+  // limb and image strides) is a multiple of N words = 8 N bytes, N even
+  const ulonglong2* ps = (const ulonglong2*)(s.p + c * s.comp_stride + l * s.limb_stride);
+  ulonglong2* pd = (ulonglong2*)(dst + c * d_comp + l * d_limb + (long long)i * N);
+  const int k0 = blockIdx.x * (kBlk * kGatherU) + threadIdx.x;
+  ulonglong2 v[kGatherU];
+#pragma unroll
+  for (int u = 0; u < kGatherU; ++u) v[u] = ps[k0 + u * kBlk];
+#pragma unroll
+  for (int u = 0; u < kGatherU; ++u) pd[k0 + u * kBlk] = v[u];
+}
+
 // ct x ct tensor: d0 = a0 b0, d1 = a0 b1 + a1 b0, d2 = a1 b1  (a, b: 2 comps; d: 3 comps)
 __global__ void __launch_bounds__(256) tensor_kernel(LimbSet d, LimbSet a, LimbSet b,
                                                      const DeviceTables* __restrict__ tb, int N) {
@@ -996,6 +1024,15 @@ int orion_launch_ew(int op, const LimbSet& o, const LimbSet& a, const LimbSet& b
 #undef CASE
     default: return -1;
   }
+  return 0;
+}
+
+int orion_launch_gather(u64* dst, long long d_comp, long long d_limb, int nimg, int nlimb, const GatherTable& T,
+                        int N, hipStream_t st) {
+  constexpr int per = 2 * kBlk * kGatherU;  // coefficients per workgroup
+  if (nimg < 1 || nimg > ORION_MAXGATHER || nlimb < 1 || 2 * nlimb > 65535 || N < per || N % per) return -1;
+  hipLaunchKernelGGL(gather_images_kernel, dim3(N / per, nimg, 2 * nlimb), dim3(kBlk), 0, st, dst, d_comp, d_limb,
+                     nlimb, T, N);
   return 0;
 }
 

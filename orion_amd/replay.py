@@ -153,6 +153,53 @@ class OrionStream:
         self.lib.DeletePlaintext(pt)
         return ct
 
+    def encrypt_images(self, images):
+        """One single-image ciphertext per image, each by its own Encode +
+        Encrypt + DeletePlaintext at the stream's input level and scale -- the
+        reference frontend's one ciphertext per call (encoder.py:37-39,
+        tensors.py:143), as separately encrypting clients produce them.
+        Returns the list of handles."""
+        imgs = np.asarray(images, dtype=np.float32).reshape(len(images), -1)
+        enc = [e for e in self.input_events() if e["op"] == "Encode"][0]
+        level, scale = enc["args"][1], enc["args"][2]
+        cts = []
+        for img in imgs:
+            vals = np.zeros(self.slots, dtype=np.float32)
+            vals[:img.shape[0]] = img
+            pt = self.lib.Encode(vals, level, scale)
+            cts.append(self.lib.Encrypt(pt))
+            self.lib.DeletePlaintext(pt)
+        return cts
+
+    def forward_stacked(self, cts):
+        """net(ct) for ciphertexts that arrived one at a time: stack them into
+        one batch handle (OrionHipStackCiphertexts), run forward() once at that
+        batch, and slice the result apart again (OrionHipSliceCiphertext).
+        Returns one output handle per input, in input order (an input that is
+        itself a batch gets a batch of the same size back); the inputs stay
+        alive and unchanged, the stacked input and the batched output are
+        deleted."""
+        lib = self.lib
+        sizes = [lib.GetCiphertextBatch(c) for c in cts]
+        x = lib.stack_ciphertexts(cts)
+        out = None
+        try:
+            out = self.forward(x)
+            outs, first = [], 0
+            try:
+                for n in sizes:
+                    outs.append(lib.slice_ciphertext(out, first, n))
+                    first += n
+            except Exception:
+                for h in outs:
+                    lib.DeleteCiphertext(h)
+                raise
+            return outs
+        finally:
+            if out is not None and out != x:
+                lib.DeleteCiphertext(out)
+            lib.DeleteCiphertext(x)
+
     def reference_input(self):
         return self.arrays["input"]
 
