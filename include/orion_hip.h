@@ -333,6 +333,54 @@ unsigned long KeyBundleBytes(int withSecret);
 int ExportKeyBundle(void *dptr, int withSecret);
 int ImportKeyBundle(const void *dptr, unsigned long bytes);
 
+/* Bootstrapping keys, record by record: a scheme without the secret key (a
+ * server, a rank that took ImportKeyBundle's bundle) builds its circuits with
+ * NewBootstrapper and receives their evaluation keys from the key owner; its
+ * Bootstrap output is then the owner's bit for bit.
+ *
+ * Every circuit has a need-list, derived from the built circuit alone: the
+ * relinearisation key of the bootstrapping chain, d2s (level 0) and s2d
+ * (top level), the trace elements, the conjugation, and every baby and giant
+ * Galois element of each CoeffsToSlots / SlotsToCoeffs transform, each at the
+ * highest level the circuit uses it at.
+ *   OrionHipBootstrapPrepareKeys (needs the secret): makes every key of the
+ *     need-list that is missing or held below its needed level, at the needed
+ *     level, without running the circuit; returns the number of records held
+ *     afterwards.  Bootstrap makes and replaces no key after it.
+ *   OrionHipBootstrapMissingKeys: how many keys of the need-list are absent or
+ *     held below their needed level (0: the circuit is ready).
+ *   OrionHipBootstrapKeyCount / KeyBytes / KeyInfo: the records held, the size
+ *     of record i (header + payload; 0 on error), and its kind (1 relin, 2 d2s,
+ *     3 s2d, 4 Galois), Galois element, level and payload bytes (out4).
+ *   OrionHipExportBootstrapKey: record i into device memory of KeyBytes(i).
+ *   OrionHipImportBootstrapKey: one record from device memory.
+ * Records are ordered relin, d2s, s2d, then the Galois keys by ascending
+ * element.  The Galois keys belong to the bootstrapping chain, which circuits
+ * with the same logPs share: a circuit's records may include a sibling's keys,
+ * and importing an element already held keeps the copy made for the higher
+ * level.  A record is a 256-byte header of unsigned 64-bit words {magic
+ * "ORIONBK1", kind, Galois element, level, slot count (d2s / s2d only: they
+ * belong to one circuit; else 0), logN, Q and P prime counts of the
+ * bootstrapping chain, dnum, FNV-1a digest of its moduli, payload bytes; zero
+ * to the end} followed by the key's device words [digit][2][level+1+K][N],
+ * digit < ceil((level+1)/K).
+ *
+ * The copies run on the library stream, which is drained before the call
+ * returns (as ExportKeyBundle / ImportKeyBundle); dptr's producer must have
+ * finished on that stream's view (orion_amd/backend.py orders it).  None of
+ * these calls is allowed inside a graph capture.  Import refuses, leaving the
+ * bootstrapper unchanged and naming the check: a bad magic, a header of another
+ * chain (digest, logN, counts, dnum), a level outside the chain, a d2s / s2d
+ * record of another slot count, `bytes` below header + payload, and a slot
+ * count with no bootstrapper.  All return -1 on error (KeyBytes: 0). */
+int OrionHipBootstrapPrepareKeys(int slots);
+int OrionHipBootstrapMissingKeys(int slots);
+int OrionHipBootstrapKeyCount(int slots);
+unsigned long OrionHipBootstrapKeyBytes(int slots, int i);
+int OrionHipBootstrapKeyInfo(int slots, int i, unsigned long *out4);
+int OrionHipExportBootstrapKey(int slots, int i, void *dptr);
+int OrionHipImportBootstrapKey(int slots, const void *dptr, unsigned long bytes);
+
 /* kernel timing with HIP events on the library stream; enable: 0 = off,
  * 1 = every category, otherwise a bit mask of categories (bit 0 ntt_fwd,
  * 1 ntt_inv, 2 elementwise, 3 basis_ext, 4 ks_mac, 5 automorph, 6 tensor,

@@ -187,6 +187,13 @@ SIGNATURES = {
     "KeyBundleBytes": ([c_int], c_ulong),
     "ExportKeyBundle": ([c_void_p, c_int], c_int),
     "ImportKeyBundle": ([c_void_p, c_ulong], c_int),
+    "OrionHipBootstrapPrepareKeys": ([c_int], c_int),
+    "OrionHipBootstrapMissingKeys": ([c_int], c_int),
+    "OrionHipBootstrapKeyCount": ([c_int], c_int),
+    "OrionHipBootstrapKeyBytes": ([c_int, c_int], c_ulong),
+    "OrionHipBootstrapKeyInfo": ([c_int, c_int, P(c_ulong)], c_int),
+    "OrionHipExportBootstrapKey": ([c_int, c_int, c_void_p], c_int),
+    "OrionHipImportBootstrapKey": ([c_int, c_void_p, c_ulong], c_int),
     "OrionHipProfile": ([c_int], None),
     "OrionHipProfileRead": ([c_char_p, P(ctypes.c_long), P(c_double), P(c_double), c_int], c_int),
     "OrionHipProfileReadStrict": ([P(c_double), c_int], c_int),
@@ -405,6 +412,54 @@ class HipLibrary:
         self._chk(self.lib.OrionHipBootstrapExport(slots, w, arg, out.ctypes.data_as(c_void_p), n),
                   "OrionHipBootstrapExport")
         return out
+
+    # ---- bootstrapping keys, record by record (a scheme without the secret
+    # key imports what the key owner exports; include/orion_hip.h) ----------
+    BOOT_KEY_KINDS = {1: "relin", 2: "d2s", 3: "s2d", 4: "galois"}
+
+    def bootstrap_prepare_keys(self, slots):
+        """Make every evaluation key the circuit for `slots` needs, at the level
+        it needs it, without running the circuit (needs the secret key).
+        Returns the number of key records held afterwards."""
+        return self._chk(self.lib.OrionHipBootstrapPrepareKeys(int(slots)), "OrionHipBootstrapPrepareKeys")
+
+    def bootstrap_missing_keys(self, slots):
+        """How many keys the circuit for `slots` still lacks (0: ready to run)."""
+        return self._chk(self.lib.OrionHipBootstrapMissingKeys(int(slots)), "OrionHipBootstrapMissingKeys")
+
+    def bootstrap_key_info(self, slots):
+        """[(kind, galois element, level, payload bytes)] of the key records
+        held for `slots`, in record order; kind as in BOOT_KEY_KINDS."""
+        n = self._chk(self.lib.OrionHipBootstrapKeyCount(int(slots)), "OrionHipBootstrapKeyCount")
+        out, v = [], (c_ulong * 4)()
+        for i in range(n):
+            self._chk(self.lib.OrionHipBootstrapKeyInfo(int(slots), i, v), "OrionHipBootstrapKeyInfo")
+            out.append((int(v[0]), int(v[1]), int(v[2]), int(v[3])))
+        return out
+
+    def export_bootstrap_key(self, slots, i, device=None):
+        """Key record i of the circuit for `slots` as a new uint8 device tensor
+        (header + the key's device words)."""
+        import torch
+        n = int(self.lib.OrionHipBootstrapKeyBytes(int(slots), int(i)))
+        if n == 0:
+            raise RuntimeError(f"OrionHipBootstrapKeyBytes: {self.lib.OrionHipLastError().decode()}")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        cur, lib_s = self._before_write(out)
+        self._chk(self.lib.OrionHipExportBootstrapKey(int(slots), int(i), out.data_ptr()), "OrionHipExportBootstrapKey")
+        cur.wait_stream(lib_s)  # (the call drains the library stream; torch's readers follow it all the same)
+        return out
+
+    def import_bootstrap_key(self, slots, t):
+        """Load one key record (a contiguous uint8 device tensor, as
+        export_bootstrap_key returns it) into the circuit for `slots`."""
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == 1
+        self._before_read(t)
+        # the call drains the library stream before it returns, so the copy out
+        # of t has run: no record_stream (t may outlive the scheme and its stream)
+        self._chk(self.lib.OrionHipImportBootstrapKey(int(slots), t.data_ptr(), t.numel()),
+                  "OrionHipImportBootstrapKey")
 
     def thread_pipelines(self, n):
         """Thread-affine pipelines (OrionHipThreadPipelines): with n > 1 every

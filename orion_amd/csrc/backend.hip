@@ -3074,6 +3074,19 @@ struct Context {
       }
     return C;
   }
+  // one evaluation key of a bootstrapping circuit: the key a circuit needs
+  // (level = the highest level it is used at) or a key held (level = the level
+  // it was made for; k = its words)
+  enum { BK_RELIN = 1, BK_D2S = 2, BK_S2D = 3, BK_GALOIS = 4 };
+  struct KeyNeed {
+    int kind = 0;
+    u64 gel = 0;  // BK_GALOIS: the Galois element
+    int level = 0;
+    const Poly* k = nullptr;
+  };
+  static const char* key_kind_name(int kind) {
+    return kind == BK_RELIN ? "relin" : kind == BK_D2S ? "d2s" : kind == BK_S2D ? "s2d" : "galois";
+  }
   struct Bootstrapper {
     // Lattigo v6 bootstrapping.ParametersLiteral defaults [U]:
     // CoeffsToSlots / SlotsToCoeffs factorisation depths and prime sizes,
@@ -3096,6 +3109,7 @@ struct Context {
     long double s_y = 0;  // scale of the EvalMod output (2^60 up to rounding)
     u64 F = 1;            // ScaleDown: message times F = round(q0 / (2^8 Delta)) before ModRaise
     EvKey d2s, s2d;       // EvkDenseToSparse (level 0), EvkSparseToDense (full chain)
+    std::vector<KeyNeed> need;  // key_needs(): every evaluation key the circuit uses (made with the circuit)
   };
   // declared in this order so that the circuits (whose buffers belong to a
   // bootstrapping context's pool) are destroyed before the contexts
@@ -3215,12 +3229,104 @@ struct Context {
       upload(B->mono_i, host);
       ntt(lsq(B->mono_i, 0, 1, L - 1), false);
     }
-    {  // the ephemeral secret and its keys (genEncapsulationEvaluationKeysNew)
-      const Poly se = secret_poly(sample_ternary_h(BT::kEphH));
-      B->d2s = EvKey{gen_evk(sk, se, 0), 0};
-      B->s2d = EvKey{gen_evk(se, sk, L - 1), L - 1};
-    }
+    B->need = key_needs(*B);
+    // the keyed part; a context without the secret gets the circuit alone and
+    // receives its keys record by record (import_key_record)
+    if (have_sk) gen_circuit_keys(*B);
     return B;
+  }
+  // (on the bootstrapping context) the ephemeral secret and its keys
+  // (genEncapsulationEvaluationKeysNew)
+  void gen_circuit_keys(Bootstrapper& bt) {
+    if (!have_sk) throw std::runtime_error("bootstrapping keys need the secret key");
+    const Poly se = secret_poly(sample_ternary_h(Bootstrapper::kEphH));
+    bt.d2s = EvKey{gen_evk(sk, se, 0), 0};
+    bt.s2d = EvKey{gen_evk(se, sk, L - 1), L - 1};
+  }
+
+  // (on the bootstrapping context) every evaluation key run_circuit uses for
+  // this circuit and the highest level it uses it at, derived from the built
+  // circuit alone (host arithmetic: no secret, no device work), in record
+  // order: the relinearisation key, d2s, s2d, then the Galois keys by
+  // ascending element.  The levels follow run_circuit step by step: the trace
+  // at the top, each transform at min(ciphertext level, its own level) -- the
+  // level eval_lt runs it at -- the conjugation below CoeffsToSlots, EvalMod's
+  // polynomial and double angles in between.
+  std::vector<KeyNeed> key_needs(const Bootstrapper& bt) const {
+    typedef Bootstrapper BT;
+    std::map<u64, int> gal;
+    auto use = [&](u64 g, int level) {
+      auto it = gal.find(g);
+      if (it == gal.end()) gal[g] = level;
+      else it->second = std::max(it->second, level);
+    };
+    auto use_lt = [&](const LinTrans& T, int level) {
+      for (int b : T.babies)
+        if (b) use(galois_element(b), level);
+      for (int j : T.giants)
+        if (j) use(galois_element(j), level);
+    };
+    int level = L - 1;
+    if (bt.gap > 1)
+      for (u64 g : bt.trace_gal) use(g, level);
+    for (const LinTrans& T : bt.cts) {
+      level = std::min(level, T.level);
+      use_lt(T, level);
+      --level;  // lt_rescale
+    }
+    use(2 * (u64)N - 1, level);  // the conjugation
+    level -= BT::kDepthPoly + bt.r;  // eval_mod
+    for (const LinTrans& T : bt.stc) {
+      level = std::min(level, T.level);
+      use_lt(T, level);
+      --level;
+    }
+    std::vector<KeyNeed> v;
+    v.push_back(KeyNeed{BK_RELIN, 0, L - 1, nullptr});
+    v.push_back(KeyNeed{BK_D2S, 0, 0, nullptr});
+    v.push_back(KeyNeed{BK_S2D, 0, L - 1, nullptr});
+    for (auto& kv : gal) v.push_back(KeyNeed{BK_GALOIS, kv.first, kv.second, nullptr});
+    return v;
+  }
+  // the key records held for a circuit, in record order.  The Galois keys are
+  // the bootstrapping context's, which circuits with the same logPs share, so
+  // they may include a sibling circuit's
+  std::vector<KeyNeed> key_records(const Bootstrapper& bt) const {
+    std::vector<KeyNeed> v;
+    if (have_rlk) v.push_back(KeyNeed{BK_RELIN, 0, L - 1, &rlk});
+    if (bt.d2s.k.buf) v.push_back(KeyNeed{BK_D2S, 0, bt.d2s.level, &bt.d2s.k});
+    if (bt.s2d.k.buf) v.push_back(KeyNeed{BK_S2D, 0, bt.s2d.level, &bt.s2d.k});
+    for (auto& kv : gks) v.push_back(KeyNeed{BK_GALOIS, kv.first, kv.second.level, &kv.second.k});
+    return v;
+  }
+  // the needed keys that are absent or held below their needed level
+  std::vector<KeyNeed> missing_keys(const Bootstrapper& bt) const {
+    std::vector<KeyNeed> miss;
+    for (const KeyNeed& n : bt.need) {
+      bool ok = false;
+      if (n.kind == BK_RELIN) ok = have_rlk;
+      else if (n.kind == BK_D2S) ok = bt.d2s.k.buf && bt.d2s.level >= n.level;
+      else if (n.kind == BK_S2D) ok = bt.s2d.k.buf && bt.s2d.level >= n.level;
+      else {
+        auto it = gks.find(n.gel);
+        ok = it != gks.end() && it->second.level >= n.level;
+      }
+      if (!ok) miss.push_back(n);
+    }
+    return miss;
+  }
+  // every missing key of the need-list, made at its needed level without
+  // running the circuit (afterwards galois_key finds each key it asks for)
+  void prepare_keys(Bootstrapper& bt) {
+    no_capture("bootstrapping key generation");
+    if (!have_sk)
+      throw std::runtime_error("preparing bootstrapping keys needs the secret key (a scheme without it imports "
+                               "them: OrionHipImportBootstrapKey)");
+    if (!have_rlk) gen_relin();
+    if (!bt.d2s.k.buf || !bt.s2d.k.buf) gen_circuit_keys(bt);
+    for (const KeyNeed& n : bt.need)
+      if (n.kind == BK_GALOIS) gen_galois(n.gel, n.level);
+    HIPCHK(hipStreamSynchronize(stream));
   }
 
   Ciphertext mul_i(const Bootstrapper& bt, const Ciphertext& a) {
@@ -3312,7 +3418,6 @@ struct Context {
     if (ns < 2 || ns > N / 2 || (ns & (ns - 1)))
       throw std::runtime_error("slots must be a power of two in [2, " + std::to_string(N / 2) + "]");
     if (btps.count(ns)) return;
-    if (!have_sk) throw std::runtime_error("bootstrapping keys need the secret key");
     if (logPs.empty()) logPs = logP_bits;
     for (int b : logPs)
       if (b < 20 || b > 61) throw std::runtime_error("bootstrapping P primes must be 20..61 bits");
@@ -3339,8 +3444,12 @@ struct Context {
       bc->stream = stream;  // shared, not owned
       bc->prng = Prng(prng.next());
       bc->init_moduli(logN, m, qb, logPs, logScale, h, false);
-      bc->import_secret(secret_coeffs());
-      bc->gen_relin();
+      // a scheme without the secret key builds the chain and the circuit alone:
+      // its keys arrive from the key owner (import_key_record)
+      if (have_sk) {
+        bc->import_secret(secret_coeffs());
+        bc->gen_relin();
+      }
       it = btp_ctx.emplace(logPs, std::move(bc)).first;
     }
     btps[ns] = it->second->make_circuit(ns);
@@ -3352,6 +3461,18 @@ struct Context {
     if (it == btps.end()) throw std::runtime_error("no bootstrapper found for slot count: " + std::to_string(ns));
     Bootstrapper& bt = *it->second;
     const int B = in.poly.B;
+    // the key owner makes a missing key at its first use (gen_galois); a
+    // context without the secret must hold every key before any work is queued
+    if (!bt.bc->have_sk) {
+      const std::vector<KeyNeed> miss = bt.bc->missing_keys(bt);
+      if (!miss.empty())
+        throw std::runtime_error("bootstrapper for " + std::to_string(ns) + " slots lacks " +
+                                 std::to_string(miss.size()) + " of its " + std::to_string(bt.need.size()) +
+                                 " evaluation keys, the first: " + key_kind_name(miss[0].kind) +
+                                 " key, galois element " + std::to_string(miss[0].gel) + ", level " +
+                                 std::to_string(miss[0].level) +
+                                 " (there is no secret key: import them, OrionHipImportBootstrapKey)");
+    }
     // ScaleDown (Lattigo ScaleDown [U]): F = round(q0 / (2^LogMessageRatio
     // scale)) times the level-0 residues (an integer: no level), F from the
     // input's own scale so the message sits 2^-8 below q0 whatever its scale;
@@ -4990,6 +5111,7 @@ long OrionHipBootstrapExport(int slots, int what, long arg, void* out, unsigned 
     }
     case ORION_BTX_RLK: {
       const long cnt = 2L * b.dnum * (b.L + b.K) * b.N;
+      if (!b.have_rlk) throw std::runtime_error("the bootstrapper holds no relinearisation key yet");
       if (out) export_evk_full(b, EvKey{b.rlk, b.L - 1}, (unsigned long*)out, n);
       return cnt;
     }
@@ -5037,6 +5159,8 @@ long OrionHipBootstrapExport(int slots, int what, long arg, void* out, unsigned 
     case ORION_BTX_D2S:  // the ephemeral-secret keys (full-chain layout; EvkDenseToSparse fills level 0)
     case ORION_BTX_S2D: {
       const long cnt = 2L * b.dnum * (b.L + b.K) * b.N;
+      if (!(what == ORION_BTX_D2S ? bt.d2s : bt.s2d).k.buf)
+        throw std::runtime_error("the bootstrapper holds no ephemeral-secret keys yet");
       if (out) export_evk_full(b, what == ORION_BTX_D2S ? bt.d2s : bt.s2d, (unsigned long*)out, n);
       return cnt;
     }
@@ -5305,6 +5429,154 @@ int ImportKeyBundle(const void* dptr, unsigned long bytes) {
     c.have_sk = true;
   }
   HIPCHK(hipStreamSynchronize(c.stream));
+  return 0;
+  API_END(-1)
+}
+
+// ---- bootstrapping keys, record by record ----
+// A scheme without the secret key builds its bootstrapping circuits
+// (NewBootstrapper) and receives their evaluation keys from the key owner, one
+// self-describing record at a time (a bundle of them all would double the
+// device memory the keys take).  A record: a 256-byte header u64[32] {magic,
+// kind, galois element, level, slot count (d2s / s2d: they belong to one
+// circuit; else 0), logN, Q and P prime counts of the bootstrapping chain,
+// dnum, digest of its moduli, payload bytes}, then the key's raw device words
+// [digit][2][level+1+K][N] (EvKey).  Records come in the need-list's order:
+// relin, d2s, s2d, the Galois keys by ascending element.
+enum { BKR_HDR = 32, BKR_MAGIC_I = 0, BKR_KIND, BKR_GEL, BKR_LEVEL, BKR_SLOTS, BKR_LOGN, BKR_L, BKR_K, BKR_DNUM,
+       BKR_DIGEST, BKR_PAYLOAD, BKR_NFIELD };
+static const u64 BKR_MAGIC = 0x4f52494f4e424b31ull;  // "ORIONBK1"
+static Context::Bootstrapper& btp_of(Context& c, int slots) {
+  auto it = c.btps.find(slots);
+  if (it == c.btps.end()) throw std::runtime_error("no bootstrapper found for slot count: " + std::to_string(slots));
+  return *it->second;
+}
+static size_t evk_bytes(const Context& b, int level) {
+  return (size_t)2 * ((level + 1 + b.K - 1) / b.K) * (level + 1 + b.K) * b.N * 8;
+}
+static Context::KeyNeed btp_record(Context& c, int slots, int i, Context::Bootstrapper** btp = nullptr) {
+  Context::Bootstrapper& bt = btp_of(c, slots);
+  const std::vector<Context::KeyNeed> recs = bt.bc->key_records(bt);
+  if (i < 0 || i >= (int)recs.size())
+    throw std::runtime_error("bootstrap key record " + std::to_string(i) + " out of range: " +
+                             std::to_string(recs.size()) + " records held for " + std::to_string(slots) + " slots");
+  if (btp) *btp = &bt;
+  return recs[i];
+}
+int OrionHipBootstrapPrepareKeys(int slots) {
+  API_BEGIN
+  Context& c = ctx();
+  Context::Bootstrapper& bt = btp_of(c, slots);
+  bt.bc->prepare_keys(bt);
+  return (int)bt.bc->key_records(bt).size();
+  API_END(-1)
+}
+int OrionHipBootstrapMissingKeys(int slots) {
+  API_BEGIN
+  Context::Bootstrapper& bt = btp_of(ctx(), slots);
+  return (int)bt.bc->missing_keys(bt).size();
+  API_END(-1)
+}
+int OrionHipBootstrapKeyCount(int slots) {
+  API_BEGIN
+  Context::Bootstrapper& bt = btp_of(ctx(), slots);
+  return (int)bt.bc->key_records(bt).size();
+  API_END(-1)
+}
+unsigned long OrionHipBootstrapKeyBytes(int slots, int i) {
+  API_BEGIN
+  Context::Bootstrapper* bt = nullptr;
+  const Context::KeyNeed r = btp_record(ctx(), slots, i, &bt);
+  return (unsigned long)(BKR_HDR * 8 + evk_bytes(*bt->bc, r.level));
+  API_END(0)
+}
+int OrionHipBootstrapKeyInfo(int slots, int i, unsigned long* out4) {
+  API_BEGIN
+  if (!out4) throw std::runtime_error("null output pointer");
+  Context::Bootstrapper* bt = nullptr;
+  const Context::KeyNeed r = btp_record(ctx(), slots, i, &bt);
+  out4[0] = (unsigned long)r.kind, out4[1] = r.gel, out4[2] = (unsigned long)r.level;
+  out4[3] = (unsigned long)evk_bytes(*bt->bc, r.level);
+  return 0;
+  API_END(-1)
+}
+int OrionHipExportBootstrapKey(int slots, int i, void* dptr) {
+  API_BEGIN
+  Context& c = ctx();
+  c.no_capture("exporting a bootstrapping key");
+  if (!dptr) throw std::runtime_error("null record pointer");
+  Context::Bootstrapper* bt = nullptr;
+  const Context::KeyNeed r = btp_record(c, slots, i, &bt);
+  Context& b = *bt->bc;
+  const size_t payload = evk_bytes(b, r.level);
+  if ((size_t)r.k->ncomp * r.k->nlimb * r.k->B * b.N * 8 != payload)
+    throw std::logic_error("bootstrap key record: key buffer does not match its level");
+  u64 hdr[BKR_HDR] = {0};
+  hdr[BKR_MAGIC_I] = BKR_MAGIC, hdr[BKR_KIND] = (u64)r.kind, hdr[BKR_GEL] = r.gel, hdr[BKR_LEVEL] = (u64)r.level;
+  hdr[BKR_SLOTS] = (r.kind == Context::BK_D2S || r.kind == Context::BK_S2D) ? (u64)slots : 0;
+  hdr[BKR_LOGN] = (u64)b.logN, hdr[BKR_L] = (u64)b.L, hdr[BKR_K] = (u64)b.K, hdr[BKR_DNUM] = (u64)b.dnum;
+  hdr[BKR_DIGEST] = moduli_digest(b), hdr[BKR_PAYLOAD] = (u64)payload;
+  HIPCHK(hipMemcpyAsync(dptr, hdr, sizeof(hdr), hipMemcpyHostToDevice, b.stream));
+  HIPCHK(hipMemcpyAsync((char*)dptr + sizeof(hdr), r.k->ptr(), payload, hipMemcpyDeviceToDevice, b.stream));
+  HIPCHK(hipStreamSynchronize(b.stream));
+  return 0;
+  API_END(-1)
+}
+int OrionHipImportBootstrapKey(int slots, const void* dptr, unsigned long bytes) {
+  API_BEGIN
+  Context& c = ctx();
+  c.no_capture("importing a bootstrapping key");
+  if (!dptr) throw std::runtime_error("null record pointer");
+  Context::Bootstrapper& bt = btp_of(c, slots);
+  Context& b = *bt.bc;
+  // every check comes before the first change: a refused record leaves the
+  // bootstrapper as it was
+  if (bytes < BKR_HDR * 8) throw std::runtime_error("bootstrap key record shorter than its header");
+  u64 h[BKR_HDR];
+  HIPCHK(hipMemcpyAsync(h, dptr, sizeof(h), hipMemcpyDeviceToHost, b.stream));
+  HIPCHK(hipStreamSynchronize(b.stream));
+  if (h[BKR_MAGIC_I] != BKR_MAGIC) throw std::runtime_error("not a bootstrap key record (bad magic)");
+  if (h[BKR_LOGN] != (u64)b.logN || h[BKR_L] != (u64)b.L || h[BKR_K] != (u64)b.K || h[BKR_DNUM] != (u64)b.dnum ||
+      h[BKR_DIGEST] != moduli_digest(b))
+    throw std::runtime_error("bootstrap key record was made for another bootstrapping chain "
+                             "(logN/L/K/dnum/moduli differ)");
+  const int kind = (int)h[BKR_KIND];
+  if (h[BKR_KIND] < (u64)Context::BK_RELIN || h[BKR_KIND] > (u64)Context::BK_GALOIS)
+    throw std::runtime_error("bootstrap key record: unknown key kind " + std::to_string(h[BKR_KIND]));
+  if (h[BKR_LEVEL] >= (u64)b.L)
+    throw std::runtime_error("bootstrap key record: level " + std::to_string(h[BKR_LEVEL]) +
+                             " outside the bootstrapping chain (" + std::to_string(b.L) + " levels)");
+  const int level = (int)h[BKR_LEVEL];
+  if (kind == Context::BK_RELIN && level != b.L - 1)
+    throw std::runtime_error("bootstrap key record: a relinearisation key below the chain's top level");
+  if ((kind == Context::BK_D2S || kind == Context::BK_S2D) && h[BKR_SLOTS] != (u64)slots)
+    throw std::runtime_error(std::string("bootstrap key record: this ") + Context::key_kind_name(kind) +
+                             " key belongs to the circuit for " + std::to_string(h[BKR_SLOTS]) + " slots, not " +
+                             std::to_string(slots));
+  if (kind == Context::BK_GALOIS && (h[BKR_GEL] >= 2 * (u64)b.N || !(h[BKR_GEL] & 1)))
+    throw std::runtime_error("bootstrap key record: " + std::to_string(h[BKR_GEL]) + " is no Galois element");
+  const size_t payload = evk_bytes(b, level);
+  if (h[BKR_PAYLOAD] != (u64)payload)
+    throw std::runtime_error("bootstrap key record: payload size does not match its level");
+  if ((size_t)bytes < BKR_HDR * 8 + payload)
+    throw std::runtime_error("bootstrap key record truncated: " + std::to_string(bytes) + " bytes, header + payload " +
+                             std::to_string(BKR_HDR * 8 + payload));
+  // a key already held at this level or above stays (the Galois keys are
+  // shared by the circuits of one bootstrapping context: a sibling's record may
+  // carry a lower level)
+  EvKey* held = kind == Context::BK_D2S ? &bt.d2s : kind == Context::BK_S2D ? &bt.s2d : nullptr;
+  if (kind == Context::BK_GALOIS) {
+    auto it = b.gks.find(h[BKR_GEL]);
+    if (it != b.gks.end()) held = &it->second;
+  }
+  if (kind == Context::BK_RELIN ? b.have_rlk : (held && held->k.buf && held->level >= level)) return 0;
+  const int beta = (level + 1 + b.K - 1) / b.K;
+  Poly k = b.alloc(2 * beta, level + 1 + b.K, 1);
+  HIPCHK(hipMemcpyAsync(k.ptr(), (const char*)dptr + BKR_HDR * 8, payload, hipMemcpyDeviceToDevice, b.stream));
+  HIPCHK(hipStreamSynchronize(b.stream));
+  if (kind == Context::BK_RELIN) b.rlk = k, b.have_rlk = true;
+  else if (kind == Context::BK_GALOIS) b.gks[h[BKR_GEL]] = EvKey{k, level};
+  else *held = EvKey{k, level};
   return 0;
   API_END(-1)
 }

@@ -5,7 +5,8 @@ The reference has no distributed code at all.  Images are
 independent ciphertexts (orion/backend/python/tensors.py:143-157), so the
 forward pass needs no collective; the only exchange is the one-off broadcast
 of the key bundle (public + relinearisation + Galois keys) from the keygen
-rank.  Everything here is backend-agnostic so the same code runs over RCCL
+rank, and, for a model that bootstraps, of each bootstrapper's key records,
+one record at a time.  Everything here is backend-agnostic so the same code runs over RCCL
 ("nccl") on the GPU box and over gloo in the CPU tests.
 """
 import os
@@ -53,6 +54,29 @@ def broadcast_bundle(dist, nbytes_fn, export_fn, import_fn, device, src=0):
         import_fn(buf)
     del buf
     return nbytes
+
+
+def broadcast_bootstrap_keys(dist, count_fn, export_fn, import_fn, device, src=0):
+    """Broadcast a bootstrapper's key records from rank `src`, one at a time.
+
+    count_fn() -> int and export_fn(i) -> uint8 tensor (record i) run on src
+    only; import_fn(buf) runs on every other rank, once per record, in order.
+    The record count goes first, then each record through broadcast_bundle, so
+    at most one record is in flight beside the keys themselves (all of a
+    ResNet's bootstrapping keys in one buffer would double their memory).
+    Returns the total bytes.
+    """
+    rank = dist.get_rank()
+    n = torch.zeros(1, dtype=torch.int64, device=device)
+    if rank == src:
+        n[0] = int(count_fn())
+    dist.broadcast(n, src)
+    total = 0
+    for i in range(int(n.item())):
+        rec = export_fn(i) if rank == src else None
+        total += broadcast_bundle(dist, lambda: rec.numel(), lambda buf: buf.copy_(rec), import_fn, device, src)
+        del rec
+    return total
 
 
 def max_over_ranks(dist, seconds, device):

@@ -136,6 +136,40 @@ class OrionStream:
                 if ev["phase"] == "forward" and ev["op"] in ("RotateNew", "Rotate"):
                     lib.AddRotationKey(ev["args"][1])
 
+    # -- bootstrapping keys for a stream without the secret key -----------------
+    def bootstrap_slot_counts(self):
+        """The slot counts the model bootstraps at (the trace's NewBootstrapper
+        events), in first-seen order."""
+        seen = []
+        for ev in self._events:
+            if ev["op"] == "NewBootstrapper" and ev["args"][1] not in seen:
+                seen.append(ev["args"][1])
+        return seen
+
+    def export_bootstrap_keys(self):
+        """On the key owner, after compile(): prepare every bootstrapper's keys
+        (OrionHipBootstrapPrepareKeys) and return {slot count: [record, ...]},
+        each record a uint8 device tensor.  A large model's records are better
+        moved one at a time (lib.export_bootstrap_key, dist.broadcast_bootstrap_keys)."""
+        lib, out = self.lib, {}
+        for ns in self.bootstrap_slot_counts():
+            n = lib.bootstrap_prepare_keys(ns)
+            out[ns] = [lib.export_bootstrap_key(ns, i) for i in range(n)]
+        return out
+
+    def import_bootstrap_keys(self, records):
+        """On a stream compiled without the secret key (the scheme's bundle
+        imported, compile(gen_keys=False)): load the owner's records, as
+        export_bootstrap_keys returns them.  Raises if a circuit still lacks a key."""
+        lib = self.lib
+        for ns, recs in records.items():
+            for r in recs:
+                lib.import_bootstrap_key(ns, r)
+        for ns in self.bootstrap_slot_counts():
+            miss = lib.bootstrap_missing_keys(ns)
+            if miss:
+                raise RuntimeError(f"bootstrapper for {ns} slots still lacks {miss} keys after the import")
+
     def input_events(self):
         return [e for e in self._events if e["phase"] == "input"]
 
