@@ -8,6 +8,7 @@ Keys come from the oracle's own seeded test keygen.
 """
 import os
 import sys
+from fractions import Fraction
 
 import numpy as np
 
@@ -173,6 +174,16 @@ class CpuStream:
         r = int(a)
         return -r if x < 0 else r
 
+    @staticmethod
+    def _round_scaled(v, s):
+        """round half away from zero of float32(v) * s, formed exactly
+        (backend.hip scaled_const_residues); s: a prime (int) or a long
+        double scale"""
+        s = Fraction(int(s)) if isinstance(s, (int, np.integer)) else Fraction(*np.longdouble(s).as_integer_ratio())
+        x = Fraction(float(np.float32(v))) * s
+        r = int(abs(x) + Fraction(1, 2))
+        return -r if x < 0 else r
+
     def _const(self, v, lvl):
         return [int(v) % self.mods[j] for j in range(lvl + 1)]
 
@@ -265,7 +276,7 @@ class CpuStream:
             elif op in ("AddScalar", "AddScalarNew", "SubScalar", "SubScalarNew"):
                 x, l, s = cts[a[0]]
                 v = np.float32(a[1]) * (-1 if op.startswith("Sub") else 1)
-                k = self._const(self._round_away(LD(float(v)) * s), l)
+                k = self._const(self._round_scaled(v, s), l)
                 y = x[:, :l + 1].copy()
                 kk = np.array(k, dtype=np.uint64)[:, None]
                 y[0] = self._addmod(y[0], np.broadcast_to(kk, y[0].shape), l)
@@ -280,7 +291,7 @@ class CpuStream:
                     cts[ret] = (self._mulconst(x[:, :l + 1], self._const(int(dv), l), l), l, s)
                 else:
                     ql = LD(self.mods[l])
-                    r = self._round_away(LD(dv) * ql)
+                    r = self._round_scaled(dv, self.mods[l])
                     cts[ret] = (self._mulconst(x[:, :l + 1], self._const(r, l), l), l, s * ql)
             elif op == "EvaluatePolynomial":
                 x, l, s = cts[a[0]]

@@ -2750,6 +2750,33 @@ struct Context {
     }
     return r;
   }
+  // round(v * s) (half away from zero), formed exactly, -> residues at `level`
+  // (AddScalar's v * scale, MulScalarFloat's v * q_level; Lattigo forms both in
+  // arbitrary precision).  v = mv 2^ev with mv < 2^24 and s = ms 2^es with
+  // ms < 2^64 (a prime below 2^61 or a long double scale), so the product's
+  // mantissa fits 128 bits: the rounding is an integer shift, and a product of
+  // 2^64 or more is reduced per limb as mant 2^e
+  std::vector<u64> scaled_const_residues(float v, long double s, int level) const {
+    if (!std::isfinite(v) || !std::isfinite(s) || s <= 0) throw std::runtime_error("scalar constant is not finite");
+    const bool neg = std::signbit(v);
+    int ev, es;
+    const u64 mv = (u64)ldexpf(frexpf(fabsf(v), &ev), 24);
+    const u64 ms = (u64)ldexpl(frexpl(s, &es), 64);
+    unsigned __int128 m = (unsigned __int128)mv * ms;
+    int e = (ev - 24) + (es - 64);
+    if (e < 0) {
+      // m < 2^88: shifted by 89 or more it is below one half
+      m = -e > 88 ? 0 : ((m >> (-e - 1)) + 1) >> 1;
+      e = 0;
+    }
+    std::vector<u64> r;
+    for (int j = 0; j <= level; ++j) {
+      const u64 q = mods[j];
+      const u64 x = hm_mulmod((u64)(m % q), hm_powmod(2 % q, (u64)e, q), q);
+      r.push_back(neg && x ? q - x : x);
+    }
+    return r;
+  }
 
   // ---------------------------------------------------------------------------
   // polynomial evaluation (polyeval.go:63-84 -> Lattigo v6 he.EvaluatePolynomial,
@@ -4444,9 +4471,7 @@ int ModDropCiphertext(int id) {
 
 static Ciphertext add_scalar(Context& c, const Ciphertext& a, float v, bool inplace_target, Ciphertext* dst) {
   (void)inplace_target;
-  long double x = (long double)v * a.scale;
-  long double r = x < 0 ? -floorl(-x + 0.5L) : floorl(x + 0.5L);
-  std::vector<u64> k = c.const_residues(r, a.level);
+  std::vector<u64> k = c.scaled_const_residues(v, a.scale, a.level);
   Ciphertext o = dst ? Ciphertext() : c.new_ct(a.level, a.poly.B, a.scale);
   Ciphertext& out = dst ? *dst : o;
   c.ew1(EW_ADDC, c.lsq(out.poly, 0, 1, a.level), c.lsq(a.poly, 0, 1, a.level), &k);
@@ -4494,14 +4519,12 @@ int MulScalarIntNew(int id, int v) {
 static void mul_float(Context& c, const Ciphertext& a, Ciphertext& out, float v) {
   const double dv = (double)v;
   if (dv == floor(dv)) {
-    mul_const(c, a, out, c.const_residues((long double)dv, a.level));
+    mul_const(c, a, out, c.scaled_const_residues(v, 1.0L, a.level));
     out.scale = a.scale;
     return;
   }
   const long double ql = (long double)c.mods[a.level];
-  long double x = (long double)dv * ql;
-  long double r = x < 0 ? -floorl(-x + 0.5L) : floorl(x + 0.5L);
-  mul_const(c, a, out, c.const_residues(r, a.level));
+  mul_const(c, a, out, c.scaled_const_residues(v, ql, a.level));
   out.scale = a.scale * ql;
 }
 int MulScalarFloat(int id, float v) {

@@ -15,6 +15,25 @@ def rand_ct(rng, moduli, level, N, B=1):
     return out
 
 
+def plant_runs(x, moduli):
+    """Constant runs at the head of every limb of x [..][limbs][N] (limb j mod
+    moduli[j]): 16 coefficients of 0, 16 of 1, 16 of q - 1, so that additions,
+    subtractions and products wrap at both ends.  In place; returns x."""
+    for j in range(x.shape[-2]):
+        x[..., j, 0:16] = 0
+        x[..., j, 16:32] = 1
+        x[..., j, 32:48] = moduli[j] - 1
+    return x
+
+
+def round_half_away(x):
+    """round-half-away-from-zero of an exact rational, as a Python int (the
+    rule of the evaluator's scalar constants)."""
+    from fractions import Fraction
+    x = Fraction(x)
+    return -int(-x + Fraction(1, 2)) if x < 0 else int(x + Fraction(1, 2))
+
+
 SMALL = dict(logn=13, logq=[55, 40, 40, 40, 40, 40], logp=[60, 60])
 
 

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import SMALL, rand_ct, SchemeCache, bootstrap_keys, bootstrap_oracle
+from tests.helpers import round_half_away as _round_half_away
 
 pytestmark = pytest.mark.gpu
 
@@ -68,13 +69,6 @@ def _mul_int(a, k, orc, level):
         out[..., j, :] = np.array([(int(x) * kj) % qj for x in a[..., j, :].reshape(-1)],
                                   dtype=np.uint64).reshape(a[..., j, :].shape)
     return out
-
-
-def _round_half_away(x):
-    """round-half-away-from-zero of an exact rational (backend.hip add_scalar / mul_float)."""
-    from fractions import Fraction
-    x = Fraction(x)
-    return -int(-x + Fraction(1, 2)) if x < 0 else int(x + Fraction(1, 2))
 
 
 def test_ct_ct_ops(small):
