@@ -731,10 +731,6 @@ struct Context {
       hipEventDestroy(r.e1);
     }
     for (auto e : ev_free) hipEventDestroy(e);
-    for (auto e : cs_ev)
-      if (e) hipEventDestroy(e);
-    for (auto s : cs_stream)
-      if (s) hipStreamDestroy(s);
     if (own_stream && stream) hipStreamDestroy(stream);
   }
 
@@ -1036,8 +1032,6 @@ struct Context {
 #endif
   // 1: one limb per workgroup (ntt.hip); 2: two-pass N = 2^15 kernels (ntt2.hip)
   int ntt_impl = getenv("ORION_NTT_IMPL") ? atoi(getenv("ORION_NTT_IMPL")) : ORION_NTT_DEFAULT_IMPL;
-  // two-pass kernels: limb-transforms per chunk (0 = one launch pair for all)
-  int ntt2_chunk = getenv("ORION_NTT2_CHUNK") ? atoi(getenv("ORION_NTT2_CHUNK")) : 0;
   // N = 2^15 launches with fewer limb-transforms than this use the two-pass
   // kernels: one limb per CU leaves most of the 256 CUs idle there (8 jobs:
   // 15 vs 37 us; 64 jobs: 32 vs 40 us, float64 path).  Batched launches
@@ -1053,8 +1047,7 @@ struct Context {
   // 1: ModUp and ModDown form the extended limbs in the forward NTT's prologue
   // (NTT_PRO_BEXT) instead of a basis_ext / modup_all launch whose output the
   // NTT reads back (sources of at most 2 limbs, Standard ring), when the NTT
-  // runs on the two-pass kernels (fuse_bext); 2: on the one-pass kernel too
-  // (timing switch); 0: never
+  // runs on the two-pass kernels (fuse_bext); 0: never
   int bext_fuse = getenv("ORION_BEXT_FUSE") ? atoi(getenv("ORION_BEXT_FUSE")) : 1;
   // N = 2^15 inverse launches up to ntt2_tail_max limb-transforms whose last
   // round of one-limb workgroups would be partial (jobs / (rounds * CUs) below
@@ -1085,40 +1078,6 @@ struct Context {
     const int rounds = (jobs + n_cu - 1) / n_cu;
     return (double)jobs / ((double)rounds * n_cu) < ntt2_tail_eff;
   }
-  // timing switches: s_sleep(127) iterations (~3.4 us each) before the first
-  // job of every other CU in persistent launches of >= ntt_stagger_min rounds
-  int ntt_stagger = getenv("ORION_NTT_STAGGER") ? atoi(getenv("ORION_NTT_STAGGER")) : 0;
-  int ntt_stagger_min = getenv("ORION_NTT_STAGGER_MIN") ? atoi(getenv("ORION_NTT_STAGGER_MIN")) : 2;
-  // co-split (timing switch): a one-pass launch of >= ntt_cosplit_min jobs
-  // gives the fraction ntt_cosplit of its jobs (its tail: the float64 limbs
-  // under job order 2) to the two-pass kernels, run concurrently on a
-  // disjoint set of CUs: the one-pass kernel is bound by one job per CU with
-  // serialised phases (~45% of HBM streaming), the two-pass kernels by HBM
-  // (86-89%), so the two can share the chip.  ntt_cosplit_q quarters of every
-  // XCD's CUs take the one-pass part (CU-masked streams, joined to the
-  // context's stream by events)
-  double ntt_cosplit = getenv("ORION_NTT_COSPLIT") ? atof(getenv("ORION_NTT_COSPLIT")) : 0.0;
-  int ntt_cosplit_min = getenv("ORION_NTT_COSPLIT_MIN") ? atoi(getenv("ORION_NTT_COSPLIT_MIN")) : 512;
-  int ntt_cosplit_q = getenv("ORION_NTT_COSPLIT_Q") ? atoi(getenv("ORION_NTT_COSPLIT_Q")) : 2;
-  hipStream_t cs_stream[2] = {nullptr, nullptr};
-  hipEvent_t cs_ev[3] = {nullptr, nullptr, nullptr};
-  int cs_cus = 0;  // CUs of the one-pass side
-  void cosplit_init() {
-    if (cs_stream[0]) return;
-    const int n = cus(), words = (n + 31) / 32;
-    // bit i in the one-pass set when (i / 8) % 4 < q: a quarter-granular share
-    // of every XCD whether the mask's CUs are numbered XCD-major or interleaved
-    std::vector<uint32_t> ma(words, 0), mb(words, 0);
-    cs_cus = 0;
-    for (int i = 0; i < n; ++i) {
-      const bool a = (i / 8) % 4 < ntt_cosplit_q;
-      (a ? ma : mb)[i / 32] |= 1u << (i % 32);
-      cs_cus += a;
-    }
-    HIPCHK(hipExtStreamCreateWithCUMask(&cs_stream[0], words, ma.data()));
-    HIPCHK(hipExtStreamCreateWithCUMask(&cs_stream[1], words, mb.data()));
-    for (auto& e : cs_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
   // ORION_NTT_LOG=path: one line per NTT call ("<dispatches> <jobs> <epi> <inv>
   // <pro> <intjobs> <family>": dispatches = kernel launches of the call (1 or
   // 2); epi = the epilogue (NTT_EPI_*); pro = the prologue; intjobs =
@@ -1142,16 +1101,10 @@ struct Context {
   bool two_pass(int jobs, bool inv, int pro, int epi, bool inplace_sub) {
     if (logN == 16) return true;
     if (logN != 15 || ci) return false;
-    if (md_force) return true;
     if (ntt_impl == 2 || jobs < ntt2_below) return true;
     const bool plain = (pro == NTT_PRO_LOAD || pro == NTT_PRO_BEXT) && epi == NTT_EPI_STORE;
-    return (inv || (ntt2_tail_fwd == 1 && plain) || (ntt2_tail_fwd == 2 && !inplace_sub) ||
-            (ntt2_tail_aut && epi_aut(epi) && pro == NTT_PRO_LOAD)) &&
-           ntt2_tail(jobs);
+    return (inv || (ntt2_tail_fwd == 1 && plain) || (ntt2_tail_fwd == 2 && !inplace_sub)) && ntt2_tail(jobs);
   }
-  // 1: the partial-round rule above also moves the rotations' scatter-store
-  // ModDown NTTs (NTT_EPI_SUBSCALE_AUT[_ACC]) onto the two-pass kernels
-  int ntt2_tail_aut = getenv("ORION_NTT2_TAIL_AUT") ? atoi(getenv("ORION_NTT2_TAIL_AUT")) : 0;
   // the fused basis extension (NTT_PRO_BEXT) pays on the two-pass kernels
   // only: in the one-pass kernel, one CU per limb, every target re-forms the
   // shared y_i and float quotient and loads ns source limbs in its memory
@@ -1160,28 +1113,12 @@ struct Context {
   // from 3.0 to 2.84 ms per image
   // and at B = 64 LoLA its partial-round two-pass launches were neutral to
   // -0.5% (2089 / 2091 vs 2105 / 2097 img/s, profiles/r04d_bext_fuse_ab.txt),
-  // so it is kept to small launches (bext_fuse_below limb-transforms)
-  bool fuse_bext(int jobs, int ns, int epi) {
-    if (!bext_fuse || ns > 2 || ci) return false;
-    return bext_fuse == 2 || ((md_force || jobs <= bext_fuse_below) && two_pass(jobs, false, NTT_PRO_BEXT, epi, false));
+  // so it is kept to small launches (bext_fuse_below limb-transforms).
+  // inplace_sub: as ntt_io passes it to two_pass, so the two always agree
+  bool fuse_bext(int jobs, int ns, int epi, bool inplace_sub) {
+    return bext_fuse && ns <= 2 && !ci && jobs <= bext_fuse_below &&
+           two_pass(jobs, false, NTT_PRO_BEXT, epi, inplace_sub);
   }
-  // timing switch ORION_MODDOWN_LAT=1 (2: rotations only): every ModDown takes the fused latency
-  // path whatever its size (the gadget product's rows pass of the P limbs'
-  // INTT, their columns pass + the extension + the Q limbs' forward columns in
-  // ntt2s_ifwd_cols_p, the Q rows pass with the subtract-and-scale), instead of
-  // the one-pass INTT, basis_ext and one-pass NTT of large batches.  md_force
-  // holds while a ModDown (or its fusability test) decides its launches
-  int moddown_lat = getenv("ORION_MODDOWN_LAT") ? atoi(getenv("ORION_MODDOWN_LAT")) : 0;
-  bool md_force = false;
-  struct MdForce {
-    Context* c;
-    bool old;
-    // (2: only the rotations' ModDowns, whose one-pass scatter-store NTT is the slowest class)
-    MdForce(Context* c_, bool aut) : c(c_), old(c_->md_force) {
-      c->md_force = !c->ci && (c->moddown_lat == 1 || (c->moddown_lat == 2 && aut));
-    }
-    ~MdForce() { c->md_force = old; }
-  };
   int bext_fuse_below = getenv("ORION_BEXT_FUSE_BELOW") ? atoi(getenv("ORION_BEXT_FUSE_BELOW")) : 64;
   // src_per_job: NTT_PRO_BEXT launches, the mean source limbs read per
   // limb-transform (their algorithmic bytes are (src_per_job + 1) 8 N, + 8 N
@@ -1207,11 +1144,6 @@ struct Context {
   // 1: a rotation's NTT-domain automorphism is applied in the ModDown's final
   // NTT store (NTT_EPI_SUBSCALE_AUT) where the kernel supports it
   int ntt_aut_fuse = getenv("ORION_NTT_AUT_FUSE") ? atoi(getenv("ORION_NTT_AUT_FUSE")) : 1;
-  // 1: a one-pass launch whose last round of one-limb workgroups is partial
-  // (at most ntt_tailsplit_max jobs) runs its whole rounds on the one-pass
-  // kernel and the partial round on the two-pass kernels
-  int ntt_tailsplit = getenv("ORION_NTT_TAILSPLIT") ? atoi(getenv("ORION_NTT_TAILSPLIT")) : 0;
-  int ntt_tailsplit_max = getenv("ORION_NTT_TAILSPLIT_MAX") ? atoi(getenv("ORION_NTT_TAILSPLIT_MAX")) : 160;
   // ... as long as the sources' columns pass is not redone too often: every
   // target workgroup redoes it for its own sources, (targets x sources per
   // target) / source limbs times the INTT's own columns work (ResNet's
@@ -1223,8 +1155,7 @@ struct Context {
   // workgroup, the sources' columns redone for each (ntt2s_ifwd_cols)
   int ntt_ifuse_p = getenv("ORION_NTT_IFUSE_P") ? atoi(getenv("ORION_NTT_IFUSE_P")) : 2;
   bool on_ntt2s(int jobs, bool inv, int pro, int epi, bool inplace_sub) {
-    return (logN == 15 || logN == 16) && !ci && (md_force || jobs <= ntt2s_below) &&
-           two_pass(jobs, inv, pro, epi, inplace_sub);
+    return (logN == 15 || logN == 16) && !ci && jobs <= ntt2s_below && two_pass(jobs, inv, pro, epi, inplace_sub);
   }
   // the INTT iio (load prologue, store epilogue) and then the forward fio whose
   // BEXT / RESCALE prologue reads the INTT's output (fio.src = iio.dst); ns_max:
@@ -1297,25 +1228,6 @@ struct Context {
     const int cat = bx ? P_NTT_BEXT : inv ? P_NTT_INV : P_NTT_FWD;
     if (two_pass(io.jobs, inv, io.pro, io.epi, io.epi != NTT_EPI_STORE && io.ex.p == io.dst.p)) {
       Poly scratch;
-      // large launches in chunks of jobs through one reused compact scratch
-      // (the intermediate can stay in the Infinity Cache); the latency
-      // kernels' small launches are never chunked
-      if (ntt2_chunk > 0 && io.jobs > std::max(ntt2_chunk, ntt2s_below) && !io.ifuse) {
-        const int chunk = std::min(ntt2_chunk, io.jobs);
-        scratch = alloc(1, 1, chunk);
-        io.mid = ls(scratch, 0, 1, {0}, {0});
-        io.mid_compact = 1;
-        Scope sc(this, cat, per * io.jobs, strict * io.jobs);
-        for (int j0 = 0; j0 < io.jobs; j0 += chunk) {
-          io.job0 = j0;
-          io.njob = std::min(chunk, io.jobs - j0);
-          if (orion_launch_ntt2(logN, io, d_tb, inv, stream)) throw std::runtime_error("NTT launch failed");
-          NttIO lio = io;
-          lio.jobs = io.njob;
-          log_ntt(2, lio, inv);
-        }
-        return;
-      }
       io.mid = io.dst;
       // in-place tail: keep ex intact for pass 2; automorphism epilogue: a rows
       // workgroup stores into other rows of dst (and, accumulating, reads
@@ -1325,7 +1237,7 @@ struct Context {
         io.mid = ls(scratch, 0, io.dst.ncomp, iota(0, io.dst.nlimb), std::vector<int>(io.dst.mod, io.dst.mod + io.dst.nlimb));
       }
       Scope sc(this, cat, per * io.jobs, strict * io.jobs);
-      const bool small = md_force || io.jobs <= ntt2s_below;
+      const bool small = io.jobs <= ntt2s_below;
       if (io.ifuse && !small) throw std::runtime_error("NTT: a fused INTT columns pass needs the latency kernels");
       if (small ? orion_launch_ntt2s(logN, io, d_tb, inv, stream) : orion_launch_ntt2(logN, io, d_tb, inv, stream))
         throw std::runtime_error("NTT launch failed");
@@ -1333,67 +1245,7 @@ struct Context {
       return;
     }
     if (io.ifuse) throw std::runtime_error("NTT: a fused INTT columns pass needs the latency kernels");
-    cus();
-    if (ntt_cosplit > 0 && logN == 15 && !ci && io.jobs >= ntt_cosplit_min && !capturing) {
-      // jobs [0, j1) on the one-pass kernel (one persistent workgroup per CU
-      // of its share), jobs [j1, jobs) on the two-pass kernels through a
-      // compact scratch, concurrently on the two CU-masked streams
-      cosplit_init();
-      const int j2 = std::min(io.jobs - 1, std::max(1, (int)lround(io.jobs * ntt_cosplit))), j1 = io.jobs - j2;
-      Scope sc(this, cat, per * io.jobs, strict * io.jobs);
-      Poly scratch = alloc(1, 1, j2);
-      NttIO a = io;
-      a.njob = j1;
-      a.grid = cs_cus;
-      NttIO b = io;
-      b.mid = ls(scratch, 0, 1, {0}, {0});
-      b.mid_compact = 1;
-      b.job0 = j1;
-      b.njob = j2;
-      HIPCHK(hipEventRecord(cs_ev[0], stream));
-      HIPCHK(hipStreamWaitEvent(cs_stream[0], cs_ev[0], 0));
-      HIPCHK(hipStreamWaitEvent(cs_stream[1], cs_ev[0], 0));
-      if (orion_launch_ntt_io(logN, a, d_tb, inv, cs_stream[0])) throw std::runtime_error("NTT launch failed");
-      const bool small = j2 <= ntt2s_below;
-      if (small ? orion_launch_ntt2s(logN, b, d_tb, inv, cs_stream[1]) : orion_launch_ntt2(logN, b, d_tb, inv, cs_stream[1]))
-        throw std::runtime_error("NTT launch failed");
-      HIPCHK(hipEventRecord(cs_ev[1], cs_stream[0]));
-      HIPCHK(hipEventRecord(cs_ev[2], cs_stream[1]));
-      HIPCHK(hipStreamWaitEvent(stream, cs_ev[1], 0));
-      HIPCHK(hipStreamWaitEvent(stream, cs_ev[2], 0));
-      a.jobs = j1;
-      b.jobs = j2;
-      log_ntt(1, a, inv);
-      log_ntt(small ? 3 : 2, b, inv);
-      return;
-    }
-    const int tail = io.jobs % n_cu;
-    if (ntt_tailsplit && logN == 15 && !ci && io.jobs > n_cu && tail > 0 && tail <= ntt_tailsplit_max) {
-      // the whole rounds on the one-pass kernel, the partial last round (the
-      // fast float64 limbs: job order 2) on the two-pass kernels, which scale
-      // with the job count instead of costing a whole limb's latency on every CU
-      Scope sc(this, cat, per * io.jobs, strict * io.jobs);
-      NttIO a = io;
-      a.njob = io.jobs - tail;
-      if (orion_launch_ntt_io(logN, a, d_tb, inv, stream)) throw std::runtime_error("NTT launch failed");
-      NttIO b = io;
-      Poly scratch = alloc(1, 1, tail);
-      b.mid = ls(scratch, 0, 1, {0}, {0});
-      b.mid_compact = 1;
-      b.job0 = io.jobs - tail;
-      b.njob = tail;
-      const bool small = tail <= ntt2s_below;
-      if (small ? orion_launch_ntt2s(logN, b, d_tb, inv, stream) : orion_launch_ntt2(logN, b, d_tb, inv, stream))
-        throw std::runtime_error("NTT launch failed");
-      a.jobs = a.njob;
-      b.jobs = tail;
-      log_ntt(1, a, inv);
-      log_ntt(small ? 3 : 2, b, inv);
-      return;
-    }
-    if (ntt_stagger > 0) {
-      io.stagger = io.jobs >= ntt_stagger_min * cus() ? ntt_stagger : 0;
-    }
+    if (bx) throw std::runtime_error("NTT: a fused basis extension needs the two-pass kernels");
     // algorithmic bytes per limb-transform: read + write the limb (16 N), + 8 N
     // for the epilogue's second operand (per, above)
     Scope sc(this, cat, per * io.dst.ncomp * io.dst.nlimb * io.dst.nbatch, strict * io.dst.ncomp * io.dst.nlimb * io.dst.nbatch);
@@ -1984,7 +1836,7 @@ struct Context {
         for (int j = 0; j < nqp; ++j)
           if (!(j >= i * K && j < std::min((i + 1) * K, level + 1))) tpos.push_back(i * nqp + j), tmod.push_back(md[j]);
       const bool tset = beta * nqp <= 256 && (int)tpos.size() <= ORION_MAXLIMB;
-      if (tset && fuse_bext(nc * B * (int)tpos.size(), K, NTT_EPI_STORE)) {
+      if (tset && fuse_bext(nc * B * (int)tpos.size(), K, NTT_EPI_STORE, false)) {
         // every digit's extension formed in the prologue of one NTT over the
         // target limbs (no modup_all launch, no round trip through HBM)
         LimbSet T = ls(D, 0, nc, tpos, tmod);
@@ -2033,7 +1885,7 @@ struct Context {
       LimbSet in = ls(cinv, 0, nc, iota(lo, hi), iota(lo, hi));
       LimbSet out = ls(D, i, nc, tpos, tmod);
       out.comp_stride = dstride;
-      if (fuse_bext(nc * B * out.nlimb, hi - lo, NTT_EPI_STORE)) {  // the extension formed in the NTT's prologue
+      if (fuse_bext(nc * B * out.nlimb, hi - lo, NTT_EPI_STORE, false)) {  // the extension formed in the NTT's prologue
         NttIO io = nio(out, in);
         io.pro = NTT_PRO_BEXT;
         io.bx = T;
@@ -2102,10 +1954,9 @@ struct Context {
   // a kernel with the automorphism-scatter epilogue (NTT_EPI_SUBSCALE_AUT):
   // the one-pass kernel with the load prologue, or the radix-4 latency kernels
   bool aut_epi_ok(int jobs, int pro) {
-    if (ci || ntt_tailsplit) return false;
+    if (ci) return false;
     if (!two_pass(jobs, false, pro, NTT_EPI_SUBSCALE_AUT, false)) return logN <= 15 && pro == NTT_PRO_LOAD;
-    if (md_force || jobs <= ntt2s_below) return NTT2S_R4;
-    return pro == NTT_PRO_LOAD && ntt2_tail_aut;  // the large two-pass kernels (ntt2.hip), load prologue
+    return jobs <= ntt2s_below && NTT2S_R4;  // the large two-pass kernels (ntt2.hip) have no scatter epilogue
   }
   u64 galois_inverse(u64 g) const {
     const u64 M = nthroot;
@@ -2126,9 +1977,8 @@ struct Context {
   // after the INTT's rows pass (keyswitch, ks_mac_rows_kernel)
   bool moddown_rows_fusable(const LimbSet& x, int level, const LimbSet& out, u64 aut_g, bool aut_acc) {
     if (!mac_rows || (logN != 15 && logN != 16) || !NTT2S_R4) return false;
-    MdForce mf(this, aut_g != 0);
     const int nc = x.ncomp, B = x.nbatch, jobs = nc * B * (level + 1);
-    if (!fuse_bext(jobs, K, NTT_EPI_SUBSCALE)) return false;
+    if (!fuse_bext(jobs, K, NTT_EPI_SUBSCALE, !aut_g && out.p == x.p)) return false;
     const bool scatter = aut_g && ntt_aut_fuse && aut_epi_ok(jobs, NTT_PRO_BEXT);
     if (aut_g && !scatter) return false;
     LimbSet xp = limbs(x, level + 1, K);
@@ -2148,10 +1998,10 @@ struct Context {
   int lt_xcd = getenv("ORION_LT_XCD") ? atoi(getenv("ORION_LT_XCD")) : 1;
   void moddown(const LimbSet& x, int level, const LimbSet& out, u64 aut_g = 0, bool aut_acc = false,
                bool rows_done = false) {
-    MdForce mf(this, aut_g != 0);
     const int nc = x.ncomp, B = x.nbatch, jobs = nc * B * (level + 1);
     LimbSet xp = limbs(x, level + 1, K);
-    const bool fused = fuse_bext(jobs, K, NTT_EPI_SUBSCALE);
+    // (with aut_g the NTT never runs in place: it scatters out of place or stores to a temporary)
+    const bool fused = fuse_bext(jobs, K, NTT_EPI_SUBSCALE, !aut_g && out.p == x.p);
     const bool scatter = aut_g && ntt_aut_fuse && aut_epi_ok(jobs, fused ? NTT_PRO_BEXT : NTT_PRO_LOAD);
     Poly tmp;
     LimbSet dst = out;

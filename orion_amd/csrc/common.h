@@ -688,6 +688,7 @@ __device__ __forceinline__ u64 bext2_apply(const Bext2& c, u64 x0, u64 x1) {
 //                             ModDown's extension of the P limbs): table bx + bx_tab[l],
 //                             target bx_t[l], sources = src rows (c, bx_s0[table] + i, b),
 //                             coefficient domain -- bit-identical to basis_ext_kernel
+//                             (two-pass kernels only: ntt2.hip, ntt2s.hip)
 //   epilogue NTT_EPI_STORE:   store to row (c, l, b) of dst
 //            NTT_EPI_SUBSCALE (forward only): dst = (ex - y) * s_l, ex row (c, l, b)
 //            NTT_EPI_SUBSCALE_AUT: the same, element e stored at position aut[e]
@@ -714,13 +715,7 @@ struct NttIO {
                 // 2 = image fastest, then component, limbs in the order lord[] (slow integer-path limbs first)
   int jobs;     // ncomp * nlimb * nbatch of dst
   int pro, epi;
-  int stagger;  // persistent kernels: s_sleep(127) iterations before the first job of every other CU (timing switch)
   int ci;       // ConjugateInvariant ring: the forward folds its input, the inverse unfolds its output (ModConst::ciw)
-  // two-pass kernels, chunked: this launch covers jobs [job0, job0 + njob) and
-  // mid is a compact scratch of njob rows (row = job - job0), reused by every
-  // chunk so the intermediate can stay in the Infinity Cache
-  int job0, njob, mid_compact;
-  int grid;  // one-pass persistent launch: workgroups (0 = one per CU), e.g. a CU-masked co-split share
   u64 s[ORION_MAXLIMB], ss[ORION_MAXLIMB];
   unsigned char lord[ORION_MAXLIMB];  // order 2: dispatch order of dst's limbs
   // NTT_PRO_BEXT: the basis-extension tables, and per dst limb its table and

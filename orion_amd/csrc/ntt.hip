@@ -51,37 +51,6 @@ __device__ __forceinline__ u64 ci_fold(u64 x, u64 y, const ModConst& mc) {
   return sub_mod(x, shoup_mul(y, mc.ciw, mc.ciw_s, mc.q), mc.q);
 }
 
-// NTT_PRO_BEXT, one-pass kernel: rows 4G .. 4G+3 of the thread's 32 formed
-// by the exact basis extension, the next group's source loads in flight.  The
-// groups recurse on a template index so that every a[] index is a constant
-// (a loop over groups that is not unrolled would index a[] dynamically and put
-// the whole limb in scratch); fenced so that no group's loads are hoisted
-// ahead (the limb's 64 VGPRs leave no room for them)
-template <int G, class A, int B0>
-__device__ __forceinline__ void bext_rows(typename A::T (&a)[32], const u64 (&xa)[4], const u64 (&xb)[4], const A& ar,
-                                          const BasisExtTable* __restrict__ T, int ti, int ns,
-                                          __amdgpu_buffer_rsrc_t r0, __amdgpu_buffer_rsrc_t r1,
-                                          int t) {
-  if constexpr (G < 8) {
-    u64 na[4], nb[4];
-    if constexpr (G < 7) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        na[k] = buf_ld(r0, t * 8, ((4 * (G + 1) + k) << B0) * 8);
-        nb[k] = ns > 1 ? buf_ld(r1, t * 8, ((4 * (G + 1) + k) << B0) * 8) : 0;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      u64 x[2] = {xa[k], xb[k]}, y[2];
-      const u64 v = bext_prep<2>(T, x, y);
-      a[4 * G + k] = ar.from_u64(bext_target_sel<2>(T->tgt + ti, ns, y, v));
-    }
-    NTT_FENCE();
-    if constexpr (G < 7) bext_rows<G + 1, A, B0>(a, na, nb, ar, T, ti, ns, r0, r1, t);
-  }
-}
-
 template <class A, int LOGN, int PRO, int EPI, bool CI>
 __device__ __forceinline__ void ntt_fwd_body(const NttIO& io, int c, int l, int b, const ModConst& mc, const A& ar,
                                              __amdgpu_buffer_rsrc_t w, u32* lds, const DeviceTables* __restrict__ tb) {
@@ -106,24 +75,8 @@ __device__ __forceinline__ void ntt_fwd_body(const NttIO& io, int c, int l, int 
 #pragma unroll
       for (int k = 0; k < 32; ++k) a[k] = ar.from_u64(buf_ld(rs, t * 8, (k << B0) * 8));
     }
-  } else if constexpr (PRO == NTT_PRO_BEXT) {
-    // the exact basis extension of (at most 2) source limbs to this limb, in
-    // registers (the value basis_ext_kernel would have stored)
-    static_assert(!CI, "no fused basis extension on the ConjugateInvariant ring");
-    const int tk = arg_byte(io.bx_tab, l), ti = arg_byte(io.bx_t, l), s0 = arg_byte(io.bx_s0, tk);
-    const BasisExtTable* __restrict__ T = io.bx + tk;
-    const int ns = T->ns;
-    const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(row_ptr(io.src, c, s0, b), 0, N * 8, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r1 =
-        __builtin_amdgcn_make_buffer_rsrc(row_ptr(io.src, c, s0 + (ns > 1 ? 1 : 0), b), 0, N * 8, 0x00020000);
-    u64 xa[4], xb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      xa[k] = buf_ld(r0, t * 8, (k << B0) * 8);
-      xb[k] = ns > 1 ? buf_ld(r1, t * 8, (k << B0) * 8) : 0;
-    }
-    bext_rows<0, A, B0>(a, xa, xb, ar, T, ti, ns, r0, r1, t);
   } else {  // NTT_PRO_RESCALE (DivRoundByLastModulusNTT), fused with the NTT of every other limb
+    static_assert(PRO == NTT_PRO_RESCALE, "NTT_PRO_BEXT runs on the two-pass kernels only");
     const u64* sp = row_ptr(io.src, c, 0, b);
     const u64 qL = tb->mc[io.modL].q, h = qL >> 1;
     const u64 hm = barrett128(0, h, mc);
@@ -338,15 +291,6 @@ __device__ __forceinline__ void ntt_inv_body(const NttIO& io, int c, int l, int 
 // with one.
 // The subtract-and-scale epilogue variants keep one job per workgroup: as a
 // loop their extra live values spill (36-41 VGPRs at N = 2^15).
-// Desynchronise the CUs of a persistent launch: half of each XCD's
-// workgroups (blockIdx bit 3; workgroups go round-robin over the 8 XCDs)
-// start late, so their memory phases fall into the other half's compute
-// phases instead of all 256 CUs contending for HBM at once.
-__device__ __forceinline__ void ntt_stagger(const NttIO& io) {
-  if (io.stagger > 0 && (blockIdx.x & 8))
-    for (int i = 0; i < io.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-}
-
 // 1: the subtract-and-scale (ModDown / rescale tail) variants are persistent
 // too (they no longer spill: 1 VGPR, outside the job loop)
 #ifndef NTT_PERSIST_ALL
@@ -390,12 +334,10 @@ template <int LOGN, int PRO, int EPI, bool CI>
 __global__ void __launch_bounds__(NttGeom<LOGN>::T) ntt_fwd_kernel(NttIO io, const DeviceTables* __restrict__ tb) {
   extern __shared__ u32 lds[];
   if constexpr (FwdPersist<EPI>::value) {
-    ntt_stagger(io);
-    const int nj = io.njob > 0 ? io.njob : io.jobs;
 #pragma nounroll
-    for (int r = 0; r * (int)gridDim.x < nj; ++r) {
+    for (int r = 0; r * (int)gridDim.x < io.jobs; ++r) {
       const int job = snake_job(r, blockIdx.x, gridDim.x);
-      if (job < nj) ntt_fwd_job<LOGN, PRO, EPI, CI>(io, job, tb, lds);
+      if (job < io.jobs) ntt_fwd_job<LOGN, PRO, EPI, CI>(io, job, tb, lds);
     }
   } else {
     ntt_fwd_job<LOGN, PRO, EPI, CI>(io, blockIdx.x, tb, lds);
@@ -406,12 +348,10 @@ template <int LOGN, bool CI>
 __global__ void __launch_bounds__(NttGeom<LOGN>::T) ntt_inv_kernel(NttIO io, const DeviceTables* __restrict__ tb) {
   constexpr int N = 1 << LOGN;
   extern __shared__ u32 lds[];
-  ntt_stagger(io);
-  const int nj = io.njob > 0 ? io.njob : io.jobs;
 #pragma nounroll
-  for (int r = 0; r * (int)gridDim.x < nj; ++r) {
+  for (int r = 0; r * (int)gridDim.x < io.jobs; ++r) {
     const int job = snake_job(r, blockIdx.x, gridDim.x);
-    if (job >= nj) continue;
+    if (job >= io.jobs) continue;
     int c, l, b;
     job_of(io, job, c, l, b);
     const int mod = arg_byte(io.dst.mod, l);
@@ -440,11 +380,9 @@ int launch_ntt_ring(const NttIO& io, const DeviceTables* tb, bool inverse, hipSt
   constexpr int N = 1 << LOGN;
   const int total = io.dst.ncomp * io.dst.nlimb * io.dst.nbatch;
   if (total == 0) return 0;
-  if (io.jobs != total || io.njob < 0 || io.njob > total || io.job0 != 0) return -1;
-  const int jobs = io.njob > 0 ? io.njob : total;  // njob: the first njob jobs only (a split launch)
+  if (io.jobs != total) return -1;
   const size_t lds = (size_t)(N + N / 32) * sizeof(u32);
-  const int gmax = io.grid > 0 ? io.grid : g_ntt_grid;
-  const dim3 g(gmax > 0 && jobs > gmax ? gmax : jobs), blk(NttGeom<LOGN>::T);
+  const dim3 g(g_ntt_grid > 0 && total > g_ntt_grid ? g_ntt_grid : total), blk(NttGeom<LOGN>::T);
   if (inverse) {
     if (io.pro != NTT_PRO_LOAD || io.epi != NTT_EPI_STORE) return -1;
     hipLaunchKernelGGL((ntt_inv_kernel<LOGN, CI>), g, blk, lds, st, io, tb);
@@ -452,7 +390,7 @@ int launch_ntt_ring(const NttIO& io, const DeviceTables* tb, bool inverse, hipSt
   }
 #define FWD(P, E)                                                                                     \
   if (io.pro == P && io.epi == E) {                                                                   \
-    hipLaunchKernelGGL((ntt_fwd_kernel<LOGN, P, E, CI>), FwdPersist<E>::value ? g : dim3(jobs), blk, lds, st, io, tb); \
+    hipLaunchKernelGGL((ntt_fwd_kernel<LOGN, P, E, CI>), FwdPersist<E>::value ? g : dim3(total), blk, lds, st, io, tb); \
     return 0;                                                                                         \
   }
   FWD(NTT_PRO_LOAD, NTT_EPI_STORE)
@@ -463,10 +401,6 @@ int launch_ntt_ring(const NttIO& io, const DeviceTables* tb, bool inverse, hipSt
     FWD(NTT_PRO_LOAD, NTT_EPI_SUBSCALE_AUT_ACC)
   }
   FWD(NTT_PRO_RESCALE, NTT_EPI_SUBSCALE)
-  if constexpr (!CI) {
-    FWD(NTT_PRO_BEXT, NTT_EPI_STORE)
-    FWD(NTT_PRO_BEXT, NTT_EPI_SUBSCALE)
-  }
 #undef FWD
   return -1;
 }
@@ -489,10 +423,6 @@ void init_lds_ring() {
   set_lds_attr<LOGN, NTT_PRO_RESCALE, NTT_EPI_SUBSCALE, CI>();
   if constexpr (!CI) set_lds_attr<LOGN, NTT_PRO_LOAD, NTT_EPI_SUBSCALE_AUT, CI>();
   if constexpr (!CI) set_lds_attr<LOGN, NTT_PRO_LOAD, NTT_EPI_SUBSCALE_AUT_ACC, CI>();
-  if constexpr (!CI) {
-    set_lds_attr<LOGN, NTT_PRO_BEXT, NTT_EPI_STORE, CI>();
-    set_lds_attr<LOGN, NTT_PRO_BEXT, NTT_EPI_SUBSCALE, CI>();
-  }
   hipFuncSetAttribute((const void*)ntt_inv_kernel<LOGN, CI>, hipFuncAttributeMaxDynamicSharedMemorySize,
                       ((1 << LOGN) + (1 << LOGN) / 32) * 4);
 }

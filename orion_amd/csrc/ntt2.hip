@@ -41,15 +41,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t twr(const void* t, int bytes) 
   return __builtin_amdgcn_make_buffer_rsrc((void*)t, 0, bytes, 0x00020000);
 }
 
-// intermediate row of job (c, l, b): dst's geometry, or a compact scratch row
-__device__ __forceinline__ u64* mid_row(const NttIO& io, int job, int c, int l, int b) {
-  if (io.mid_compact) {
-    const unsigned r = __builtin_amdgcn_readfirstlane((unsigned)(job - io.job0));
-    return io.mid.p + (long long)r * io.mid.batch_stride;
-  }
-  return row_ptr(io.mid, c, l, b);
-}
-
 template <class A>
 __device__ __forceinline__ void reduce16(typename A::T (&a)[16], const A& ar) {
 #pragma unroll
@@ -65,7 +56,7 @@ __device__ __forceinline__ void reduce16(typename A::T (&a)[16], const A& ar) {
 //            stages d = LOGN-5 .. 8
 // ---------------------------------------------------------------------------
 template <class A, int LOGN, int PRO>
-__device__ __forceinline__ void fwd_cols(const NttIO& io, int job, int c, int l, int b, int tile, const ModConst& mc,
+__device__ __forceinline__ void fwd_cols(const NttIO& io, int c, int l, int b, int tile, const ModConst& mc,
                                          const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds, bool lazy,
                                          const DeviceTables* __restrict__ tb) {
   constexpr int R = LOGN - 8, RG = 1 << (R - 4), J = 1 << (R - 4), G = 16 / J;
@@ -132,7 +123,7 @@ __device__ __forceinline__ void fwd_cols(const NttIO& io, int job, int c, int l,
         }
   }
   if (!lazy) reduce16<A>(a, ar);
-  u64* mid = mid_row(io, job, c, l, b);
+  u64* mid = row_ptr(io.mid, c, l, b);
 #pragma unroll
   for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -144,12 +135,12 @@ __device__ __forceinline__ void fwd_cols(const NttIO& io, int job, int c, int l,
 // jc + 16 i) then d = 3..0 (phase 2: columns 16 ig + j, ig = t & 15)
 // ---------------------------------------------------------------------------
 template <class A, int LOGN, int EPI>
-__device__ __forceinline__ void fwd_rows(const NttIO& io, int job, int c, int l, int b, int tile, const ModConst& mc,
+__device__ __forceinline__ void fwd_rows(const NttIO& io, int c, int l, int b, int tile, const ModConst& mc,
                                          const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds, bool lazy) {
   const int t = threadIdx.x, rr = t >> 4, jc = t & 15;
   const int row = tile * 16 + rr;
   typename A::T a[16];
-  const u64* mid = mid_row(io, job, c, l, b) + (row << 8);
+  const u64* mid = row_ptr(io.mid, c, l, b) + (row << 8);
 #pragma unroll
   for (int i = 0; i < 16; ++i) a[i] = from_bits<typename A::T>(mid[jc + 16 * i]);
 #pragma unroll
@@ -181,34 +172,8 @@ __device__ __forceinline__ void fwd_rows(const NttIO& io, int job, int c, int l,
 #pragma unroll
     for (int j = 0; j < 16; j += 2)
       *(ulonglong2*)(dst + j) = make_ulonglong2(ar.final_fwd(a[j]), ar.final_fwd(a[j + 1]));
-  } else if constexpr (epi_aut(EPI)) {
-    // (ex - y) * s_l stored at position aut[e] of the limb (added to the word
-    // there for _ACC): the rotation's NTT-domain automorphism in the ModDown's
-    // store, as in the one-pass and latency kernels
-    const u64* ex = row_ptr(io.ex, c, l, b) + (row << 8) + 16 * jc;
-    const u32* ai = io.aut + (row << 8) + 16 * jc;
-    u64* const d = row_ptr(io.dst, c, l, b);
-    const u64 s = io.s[l], ss = io.ss[l];
-#pragma unroll
-    for (int j = 0; j < 16; j += 4) {
-      const uint4 ix = *(const uint4*)(ai + j);
-      const ulonglong2 e01 = *(const ulonglong2*)(ex + j), e23 = *(const ulonglong2*)(ex + j + 2);
-      u64 o0 = shoup_mul(sub_mod(e01.x, ar.final_fwd(a[j]), mc.q), s, ss, mc.q);
-      u64 o1 = shoup_mul(sub_mod(e01.y, ar.final_fwd(a[j + 1]), mc.q), s, ss, mc.q);
-      u64 o2 = shoup_mul(sub_mod(e23.x, ar.final_fwd(a[j + 2]), mc.q), s, ss, mc.q);
-      u64 o3 = shoup_mul(sub_mod(e23.y, ar.final_fwd(a[j + 3]), mc.q), s, ss, mc.q);
-      if constexpr (EPI == NTT_EPI_SUBSCALE_AUT_ACC) {
-        o0 = add_mod(o0, d[ix.x], mc.q);
-        o1 = add_mod(o1, d[ix.y], mc.q);
-        o2 = add_mod(o2, d[ix.z], mc.q);
-        o3 = add_mod(o3, d[ix.w], mc.q);
-      }
-      d[ix.x] = o0;
-      d[ix.y] = o1;
-      d[ix.z] = o2;
-      d[ix.w] = o3;
-    }
   } else {  // NTT_EPI_SUBSCALE: dst = (ex - y) * s_l
+    static_assert(EPI == NTT_EPI_SUBSCALE, "no automorphism-scatter epilogue on these kernels");
     const u64* ex = row_ptr(io.ex, c, l, b) + (row << 8) + 16 * jc;
     const u64 s = io.s[l], ss = io.ss[l];
 #pragma unroll
@@ -226,7 +191,7 @@ __device__ __forceinline__ void fwd_rows(const NttIO& io, int job, int c, int l,
 // every other stage and every phase ends with a full reduction
 // ---------------------------------------------------------------------------
 template <class A, int LOGN>
-__device__ __forceinline__ void inv_rows(const NttIO& io, int job, int c, int l, int b, int tile, const A& ar,
+__device__ __forceinline__ void inv_rows(const NttIO& io, int c, int l, int b, int tile, const A& ar,
                                          __amdgpu_buffer_rsrc_t tw, u64* lds) {
   const int t = threadIdx.x, rr = t >> 4, jc = t & 15;
   const int row = tile * 16 + rr;
@@ -265,7 +230,7 @@ __device__ __forceinline__ void inv_rows(const NttIO& io, int job, int c, int l,
               (k & 1) == 1);
   }
   reduce16<A>(a, ar);
-  u64* mid = mid_row(io, job, c, l, b) + (row << 8);
+  u64* mid = row_ptr(io.mid, c, l, b) + (row << 8);
 #pragma unroll
   for (int i = 0; i < 16; ++i) mid[jc + 16 * i] = to_bits(a[i]);
 }
@@ -273,13 +238,13 @@ __device__ __forceinline__ void inv_rows(const NttIO& io, int job, int c, int l,
 // inverse, cols pass (second): stages d = 8..LOGN-5 (rows J (rg + RG g) + j),
 // then d = LOGN-4..LOGN-1 (rows rg + RG i, wave-uniform twiddles), times N^-1
 template <class A, int LOGN>
-__device__ __forceinline__ void inv_cols(const NttIO& io, int job, int c, int l, int b, int tile, const A& ar,
+__device__ __forceinline__ void inv_cols(const NttIO& io, int c, int l, int b, int tile, const A& ar,
                                          __amdgpu_buffer_rsrc_t tw, u64* lds) {
   constexpr int R = LOGN - 8, RG = 1 << (R - 4), J = 1 << (R - 4), G = 16 / J;
   const int t = threadIdx.x, cl = t & 15, rg = t >> 4;
   const int col = tile * 16 + cl;
   typename A::T a[16];
-  const u64* mid = mid_row(io, job, c, l, b);
+  const u64* mid = row_ptr(io.mid, c, l, b);
 #pragma unroll
   for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -333,16 +298,15 @@ __global__ void __launch_bounds__(N2<LOGN>::ATHREADS) __attribute__((amdgpu_wave
 ntt2_fwd_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[(1 << N2<LOGN>::R) * A_STRIDE];
   int c, l, b;
-  const int job = io.job0 + (blockIdx.x >> 4);
-  job_of(io, job, c, l, b);
+  job_of(io, blockIdx.x >> 4, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
   const bool lazy = mc.bar_k <= 41;
   if (mc.f64)
-    fwd_cols<F64Arith, LOGN, PRO>(io, job, c, l, b, blockIdx.x & 15, mc, F64Arith(mc), twr(tb->fwd_d[mod], (8 << LOGN)),
+    fwd_cols<F64Arith, LOGN, PRO>(io, c, l, b, blockIdx.x & 15, mc, F64Arith(mc), twr(tb->fwd_d[mod], (8 << LOGN)),
                                   lds, lazy, tb);
   else
-    fwd_cols<IntArith, LOGN, PRO>(io, job, c, l, b, blockIdx.x & 15, mc, IntArith(mc), twr(tb->fwd[mod], (16 << LOGN)),
+    fwd_cols<IntArith, LOGN, PRO>(io, c, l, b, blockIdx.x & 15, mc, IntArith(mc), twr(tb->fwd[mod], (16 << LOGN)),
                                   lds, true, tb);
 }
 
@@ -351,15 +315,14 @@ __global__ void __launch_bounds__(256) ntt2_fwd_rows(NttIO io, const DeviceTable
   __shared__ u64 lds[16 * B_STRIDE];
   constexpr int T = N2<LOGN>::BTILES;
   int c, l, b;
-  const int job = io.job0 + blockIdx.x / T;
-  job_of(io, job, c, l, b);
+  job_of(io, blockIdx.x / T, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
   if (mc.f64)
-    fwd_rows<F64Arith, LOGN, EPI>(io, job, c, l, b, blockIdx.x % T, mc, F64Arith(mc), twr(tb->fwd_d[mod], (8 << LOGN)),
+    fwd_rows<F64Arith, LOGN, EPI>(io, c, l, b, blockIdx.x % T, mc, F64Arith(mc), twr(tb->fwd_d[mod], (8 << LOGN)),
                                   lds, mc.bar_k <= 41);
   else
-    fwd_rows<IntArith, LOGN, EPI>(io, job, c, l, b, blockIdx.x % T, mc, IntArith(mc), twr(tb->fwd[mod], (16 << LOGN)),
+    fwd_rows<IntArith, LOGN, EPI>(io, c, l, b, blockIdx.x % T, mc, IntArith(mc), twr(tb->fwd[mod], (16 << LOGN)),
                                   lds, true);
 }
 
@@ -368,28 +331,26 @@ __global__ void __launch_bounds__(256) ntt2_inv_rows(NttIO io, const DeviceTable
   __shared__ u64 lds[16 * B_STRIDE];
   constexpr int T = N2<LOGN>::BTILES;
   int c, l, b;
-  const int job = io.job0 + blockIdx.x / T;
-  job_of(io, job, c, l, b);
+  job_of(io, blockIdx.x / T, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
   if (mc.f64)
-    inv_rows<F64Arith, LOGN>(io, job, c, l, b, blockIdx.x % T, F64Arith(mc), twr(tb->inv_d[mod], (8 << LOGN)), lds);
+    inv_rows<F64Arith, LOGN>(io, c, l, b, blockIdx.x % T, F64Arith(mc), twr(tb->inv_d[mod], (8 << LOGN)), lds);
   else
-    inv_rows<IntArith, LOGN>(io, job, c, l, b, blockIdx.x % T, IntArith(mc), twr(tb->inv[mod], (16 << LOGN)), lds);
+    inv_rows<IntArith, LOGN>(io, c, l, b, blockIdx.x % T, IntArith(mc), twr(tb->inv[mod], (16 << LOGN)), lds);
 }
 
 template <int LOGN>
 __global__ void __launch_bounds__(N2<LOGN>::ATHREADS) ntt2_inv_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[(1 << N2<LOGN>::R) * A_STRIDE];
   int c, l, b;
-  const int job = io.job0 + (blockIdx.x >> 4);
-  job_of(io, job, c, l, b);
+  job_of(io, blockIdx.x >> 4, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
   if (mc.f64)
-    inv_cols<F64Arith, LOGN>(io, job, c, l, b, blockIdx.x & 15, F64Arith(mc), twr(tb->inv_d[mod], (8 << LOGN)), lds);
+    inv_cols<F64Arith, LOGN>(io, c, l, b, blockIdx.x & 15, F64Arith(mc), twr(tb->inv_d[mod], (8 << LOGN)), lds);
   else
-    inv_cols<IntArith, LOGN>(io, job, c, l, b, blockIdx.x & 15, IntArith(mc), twr(tb->inv[mod], (16 << LOGN)), lds);
+    inv_cols<IntArith, LOGN>(io, c, l, b, blockIdx.x & 15, IntArith(mc), twr(tb->inv[mod], (16 << LOGN)), lds);
 }
 
 template <int LOGN>
@@ -397,16 +358,14 @@ int launch2(const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t s
   const int total = io.dst.ncomp * io.dst.nlimb * io.dst.nbatch;
   if (total == 0) return 0;
   if (io.jobs != total) return -1;
-  const int jobs = io.njob ? io.njob : total;
-  if (io.job0 < 0 || io.job0 + jobs > total) return -1;
-  if (io.mid_compact && io.mid.batch_stride < (1 << LOGN)) return -1;
-  const dim3 ga(jobs * 16), ba(N2<LOGN>::ATHREADS), gb(jobs * N2<LOGN>::BTILES), bb(256);
+  const dim3 ga(total * 16), ba(N2<LOGN>::ATHREADS), gb(total * N2<LOGN>::BTILES), bb(256);
   if (inverse) {
     if (io.pro != NTT_PRO_LOAD || io.epi != NTT_EPI_STORE) return -1;
     hipLaunchKernelGGL(ntt2_inv_rows<LOGN>, gb, bb, 0, st, io, tb);
     hipLaunchKernelGGL(ntt2_inv_cols<LOGN>, ga, ba, 0, st, io, tb);
     return 0;
   }
+  if (io.epi != NTT_EPI_STORE && io.epi != NTT_EPI_SUBSCALE) return -1;  // (no automorphism-scatter epilogue here)
   if (io.pro == NTT_PRO_LOAD)
     hipLaunchKernelGGL((ntt2_fwd_cols<LOGN, NTT_PRO_LOAD>), ga, ba, 0, st, io, tb);
   else if (io.pro == NTT_PRO_BEXT && !io.ci)
@@ -417,14 +376,8 @@ int launch2(const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t s
     return -1;
   if (io.epi == NTT_EPI_STORE)
     hipLaunchKernelGGL((ntt2_fwd_rows<LOGN, NTT_EPI_STORE>), gb, bb, 0, st, io, tb);
-  else if (io.epi == NTT_EPI_SUBSCALE)
-    hipLaunchKernelGGL((ntt2_fwd_rows<LOGN, NTT_EPI_SUBSCALE>), gb, bb, 0, st, io, tb);
-  else if (io.epi == NTT_EPI_SUBSCALE_AUT && io.aut)
-    hipLaunchKernelGGL((ntt2_fwd_rows<LOGN, NTT_EPI_SUBSCALE_AUT>), gb, bb, 0, st, io, tb);
-  else if (io.epi == NTT_EPI_SUBSCALE_AUT_ACC && io.aut)
-    hipLaunchKernelGGL((ntt2_fwd_rows<LOGN, NTT_EPI_SUBSCALE_AUT_ACC>), gb, bb, 0, st, io, tb);
   else
-    return -1;
+    hipLaunchKernelGGL((ntt2_fwd_rows<LOGN, NTT_EPI_SUBSCALE>), gb, bb, 0, st, io, tb);
   return 0;
 }
 

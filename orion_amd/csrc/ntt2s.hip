@@ -58,14 +58,6 @@ struct S2 {
 // lower index of butterfly k of a stage on bit `bit` (pairs lo, lo + 2^bit)
 [[maybe_unused]] __device__ __forceinline__ int lo_of(int k, int bit) { return ((k >> bit) << (bit + 1)) | (k & ((1 << bit) - 1)); }
 
-__device__ __forceinline__ u64* mid_row_s(const NttIO& io, int job, int c, int l, int b) {
-  if (io.mid_compact) {
-    const unsigned r = __builtin_amdgcn_readfirstlane((unsigned)(job - io.job0));
-    return io.mid.p + (long long)r * io.mid.batch_stride;
-  }
-  return row_ptr(io.mid, c, l, b);
-}
-
 // forward prologue: element e of job (c, l, b)
 template <class A, int PRO>
 __device__ __forceinline__ typename A::T fwd_load(const NttIO& io, int c, int l, int b, int e, const ModConst& mc,
@@ -93,7 +85,7 @@ __device__ __forceinline__ typename A::T fwd_load(const NttIO& io, int c, int l,
 // i = lo >> (rb + 1) = k >> rb is w[(N >> (d+1)) + i]
 // ---------------------------------------------------------------------------
 template <class A, int LOGN>
-__device__ __forceinline__ void s_fwd_cols_core(const NttIO& io, int job, int c, int l, int b, int tile,
+__device__ __forceinline__ void s_fwd_cols_core(const NttIO& io, int c, int l, int b, int tile,
                                                 typename A::T x, typename A::T y, const A& ar,
                                                 __amdgpu_buffer_rsrc_t tw, u64* lds) {
   constexpr int N = 1 << LOGN, R = S2<LOGN>::R, CW = S2<LOGN>::CW;
@@ -120,26 +112,26 @@ __device__ __forceinline__ void s_fwd_cols_core(const NttIO& io, int job, int c,
     }
   }
   x = ar.reduce_round(x), y = ar.reduce_round(y);
-  u64* mid = mid_row_s(io, job, c, l, b);
+  u64* mid = row_ptr(io.mid, c, l, b);
   const int lo = 2 * k;  // the last stage's pair: rows 2k, 2k + 1
   mid[col + (lo << 8)] = to_bits(x);
   mid[col + ((lo + 1) << 8)] = to_bits(y);
 }
 template <class A, int LOGN, int PRO>
-__device__ __forceinline__ void s_fwd_cols(const NttIO& io, int job, int c, int l, int b, int tile, const ModConst& mc,
+__device__ __forceinline__ void s_fwd_cols(const NttIO& io, int c, int l, int b, int tile, const ModConst& mc,
                                            const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds,
                                            const DeviceTables* __restrict__ tb) {
   constexpr int CW = S2<LOGN>::CW, H = S2<LOGN>::H;
   const int t = threadIdx.x, cl = t % CW, k = t / CW, col = tile * CW + cl;
   const typename A::T x = fwd_load<A, PRO>(io, c, l, b, col + (k << 8), mc, ar, tb);
   const typename A::T y = fwd_load<A, PRO>(io, c, l, b, col + ((k + H) << 8), mc, ar, tb);
-  s_fwd_cols_core<A, LOGN>(io, job, c, l, b, tile, x, y, ar, tw, lds);
+  s_fwd_cols_core<A, LOGN>(io, c, l, b, tile, x, y, ar, tw, lds);
 }
 
 // forward rows pass: thread (rr, kk) owns butterfly kk of row rr in each of
 // the stages d = 7 .. 0; twiddle w[(N >> (d+1)) + ((row << (7-d)) | (kk >> d))]
 template <class A, int LOGN, int EPI>
-__device__ __forceinline__ void s_fwd_rows(const NttIO& io, int job, int c, int l, int b, int tile, const ModConst& mc,
+__device__ __forceinline__ void s_fwd_rows(const NttIO& io, int c, int l, int b, int tile, const ModConst& mc,
                                            const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds) {
   constexpr int N = 1 << LOGN;
   const int t = threadIdx.x, rr = t >> 7, kk = t & 127, row = tile * S2<LOGN>::RW + rr;
@@ -149,7 +141,7 @@ __device__ __forceinline__ void s_fwd_rows(const NttIO& io, int job, int c, int 
     const int d = 7 - s;
     w[s] = ar.tw(tw, (row << (7 - d)) | (kk >> d), N >> (d + 1));
   }
-  const u64* mid = mid_row_s(io, job, c, l, b) + (row << 8);
+  const u64* mid = row_ptr(io.mid, c, l, b) + (row << 8);
   typename A::T x = from_bits<typename A::T>(mid[kk]);
   typename A::T y = from_bits<typename A::T>(mid[kk + 128]);
   u64* lr = lds + rr * 256;
@@ -183,7 +175,7 @@ __device__ __forceinline__ void s_fwd_rows(const NttIO& io, int job, int c, int 
 
 // inverse rows pass (first): stages d = 0 .. 7, GS; the sum reduced every other stage
 template <class A, int LOGN>
-__device__ __forceinline__ void s_inv_rows(const NttIO& io, int job, int c, int l, int b, int tile, const A& ar,
+__device__ __forceinline__ void s_inv_rows(const NttIO& io, int c, int l, int b, int tile, const A& ar,
                                            __amdgpu_buffer_rsrc_t tw, u64* lds) {
   constexpr int N = 1 << LOGN;
   const int t = threadIdx.x, rr = t >> 7, kk = t & 127, row = tile * S2<LOGN>::RW + rr;
@@ -208,21 +200,21 @@ __device__ __forceinline__ void s_inv_rows(const NttIO& io, int job, int c, int 
     }
   }
   x = ar.reduce_round(x), y = ar.reduce_round(y);
-  u64* mid = mid_row_s(io, job, c, l, b) + (row << 8);
+  u64* mid = row_ptr(io.mid, c, l, b) + (row << 8);
   mid[kk] = to_bits(x);  // the last stage's pair: columns kk, kk + 128
   mid[kk + 128] = to_bits(y);
 }
 
 // inverse cols pass (second): stages d = 8 .. LOGN-1 (row bit rb = d - 8), times N^-1
 template <class A, int LOGN>
-__device__ __forceinline__ void s_inv_cols(const NttIO& io, int job, int c, int l, int b, int tile, const A& ar,
+__device__ __forceinline__ void s_inv_cols(const NttIO& io, int c, int l, int b, int tile, const A& ar,
                                            __amdgpu_buffer_rsrc_t tw, u64* lds) {
   constexpr int N = 1 << LOGN, R = S2<LOGN>::R, CW = S2<LOGN>::CW, H = S2<LOGN>::H;
   const int t = threadIdx.x, cl = t % CW, k = t / CW, col = tile * CW + cl;
   typename A::W w[R];
 #pragma unroll
   for (int rb = 0; rb < R; ++rb) w[rb] = ar.tw(tw, k >> rb, N >> (rb + 9));
-  const u64* mid = mid_row_s(io, job, c, l, b);
+  const u64* mid = row_ptr(io.mid, c, l, b);
   typename A::T x = from_bits<typename A::T>(mid[col + ((2 * k) << 8)]);
   typename A::T y = from_bits<typename A::T>(mid[col + ((2 * k + 1) << 8)]);
 #pragma unroll
@@ -345,7 +337,7 @@ __device__ __forceinline__ void s_fwd_cols4_tw(const A& ar, __amdgpu_buffer_rsrc
   if (R & 1) wl[0] = ar.tw(tw, 2 * j, N >> 9), wl[1] = ar.tw(tw, 2 * j + 1, N >> 9);
 }
 template <class A, int LOGN>
-__device__ __forceinline__ void s_fwd_cols4_run(const NttIO& io, int job, int c, int l, int b, int tile,
+__device__ __forceinline__ void s_fwd_cols4_run(const NttIO& io, int c, int l, int b, int tile,
                                                 typename A::T (&x)[4], const A& ar,
                                                 const typename A::W (&wa)[S2<LOGN>::R / 2],
                                                 const typename A::W (&wb)[S2<LOGN>::R / 2],
@@ -353,6 +345,9 @@ __device__ __forceinline__ void s_fwd_cols4_run(const NttIO& io, int job, int c,
                                                 const typename A::W (&wl)[2], u64* lds, int t) {
   constexpr int R = S2<LOGN>::R, CW = S2<LOGN>::CW, NS = R / 2;
   const int cl = t % CW, j = t / CW, col = tile * CW + cl;
+  // (wave-uniform; formed ahead of the stages: formed at the store, the
+  // N = 2^16 ntt2s_ifwd_cols_p kernels took 66 VGPRs, 7 waves instead of 8)
+  u64* mid = row_ptr(io.mid, c, l, b);
 #pragma unroll
   for (int st = 0; st < NS; ++st) {
     const int hb = R - 1 - 2 * st, lb = hb - 1;
@@ -380,21 +375,20 @@ __device__ __forceinline__ void s_fwd_cols4_run(const NttIO& io, int job, int c,
     if (!(NTT2S_ABLATE & 4)) ar.ct(x[0], x[1], wl[0]);
     if (!(NTT2S_ABLATE & 4)) ar.ct(x[2], x[3], wl[1]);
   }
-  u64* mid = mid_row_s(io, job, c, l, b);
 #pragma unroll
   for (int i = 0; i < 4; ++i) mid[col + ((4 * j + i) << 8)] = to_bits(ar.reduce_round(x[i]));
 }
 template <class A, int LOGN>
-__device__ __forceinline__ void s_fwd_cols4_core(const NttIO& io, int job, int c, int l, int b, int tile,
+__device__ __forceinline__ void s_fwd_cols4_core(const NttIO& io, int c, int l, int b, int tile,
                                                  typename A::T (&x)[4], const A& ar, __amdgpu_buffer_rsrc_t tw,
                                                  u64* lds, int t) {
   constexpr int NS = S2<LOGN>::R / 2;
   typename A::W wa[NS], wb[NS], wc[NS], wl[2];
   s_fwd_cols4_tw<A, LOGN>(ar, tw, t / S2<LOGN>::CW, wa, wb, wc, wl);
-  s_fwd_cols4_run<A, LOGN>(io, job, c, l, b, tile, x, ar, wa, wb, wc, wl, lds, t);
+  s_fwd_cols4_run<A, LOGN>(io, c, l, b, tile, x, ar, wa, wb, wc, wl, lds, t);
 }
 template <class A, int LOGN, int PRO>
-__device__ __forceinline__ void s_fwd_cols4(const NttIO& io, int job, int c, int l, int b, int tile,
+__device__ __forceinline__ void s_fwd_cols4(const NttIO& io, int c, int l, int b, int tile,
                                             const ModConst& mc, const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds,
                                             const DeviceTables* __restrict__ tb) {
   constexpr int R = S2<LOGN>::R, CW = S2<LOGN>::CW, Q = 1 << (R - 2);
@@ -418,15 +412,15 @@ __device__ __forceinline__ void s_fwd_cols4(const NttIO& io, int job, int c, int
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = fwd_load<A, PRO>(io, c, l, b, col + ((j + i * Q) << 8), mc, ar, tb);
   }
-  s_fwd_cols4_core<A, LOGN>(io, job, c, l, b, tile, x, ar, tw, lds, (int)threadIdx.x);
+  s_fwd_cols4_core<A, LOGN>(io, c, l, b, tile, x, ar, tw, lds, (int)threadIdx.x);
 }
 
 // forward rows pass, radix 4: thread (rr, kk), kk < 64
 template <class A, int LOGN, int EPI>
-__device__ __forceinline__ void s_fwd_rows4(const NttIO& io, int job, int c, int l, int b, int tile, const ModConst& mc,
+__device__ __forceinline__ void s_fwd_rows4(const NttIO& io, int c, int l, int b, int tile, const ModConst& mc,
                                             const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds) {
   const int t = threadIdx.x, rr = t >> 6, kk = t & 63, row = tile * S2<LOGN>::RW + rr;
-  const u64* mid = mid_row_s(io, job, c, l, b) + (row << 8);
+  const u64* mid = row_ptr(io.mid, c, l, b) + (row << 8);
   typename A::T x[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) x[i] = from_bits<typename A::T>(mid[kk + 64 * i]);
@@ -479,13 +473,13 @@ __device__ __forceinline__ void s_fwd_rows4(const NttIO& io, int job, int c, int
 // inverse rows pass, radix 4 (first): steps on bits (0, 1) .. (6, 7)
 // (inv_rows4_core, ntt2s_rows.h)
 template <class A, int LOGN>
-__device__ __forceinline__ void s_inv_rows4(const NttIO& io, int job, int c, int l, int b, int tile, const A& ar,
+__device__ __forceinline__ void s_inv_rows4(const NttIO& io, int c, int l, int b, int tile, const A& ar,
                                             __amdgpu_buffer_rsrc_t tw, u64* lds) {
   const int t = threadIdx.x, rr = t >> 6, kk = t & 63, row = tile * S2<LOGN>::RW + rr;
   const u64* src = row_ptr(io.src, c, l, b) + (row << 8) + 4 * kk;
   const ulonglong2 v01 = *(const ulonglong2*)src, v23 = *(const ulonglong2*)(src + 2);
   typename A::T x[4] = {ar.from_u64(v01.x), ar.from_u64(v01.y), ar.from_u64(v23.x), ar.from_u64(v23.y)};
-  inv_rows4_core<A, LOGN>(x, row, kk, ar, tw, lds + rr * 256, mid_row_s(io, job, c, l, b) + (row << 8));
+  inv_rows4_core<A, LOGN>(x, row, kk, ar, tw, lds + rr * 256, row_ptr(io.mid, c, l, b) + (row << 8));
 }
 
 // inverse columns pass, radix 4 (second), up to two source limbs interleaved
@@ -602,7 +596,7 @@ template <int LOGN, int PRO>
 __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
     ntt2s_ifwd_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[2 * (S2<LOGN>::CW << S2<LOGN>::R)];
-  const int job = io.job0 + blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
+  const int job = blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
   int c, l, b;
   job_of(io, job, c, l, b);
   // the sources: limbs sl0 (, sl0 + 1) of src, inverse intermediate in imid
@@ -660,9 +654,9 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
       typename A::T x[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) x[i] = ar.from_u64(o[i]);
-      s_fwd_cols4_core<A, LOGN>(io, job, c, l, b, tile, x, ar, tw, lds, (int)threadIdx.x);
+      s_fwd_cols4_core<A, LOGN>(io, c, l, b, tile, x, ar, tw, lds, (int)threadIdx.x);
     } else {
-      s_fwd_cols_core<A, LOGN>(io, job, c, l, b, tile, ar.from_u64(o[0]), ar.from_u64(o[1]), ar, tw, lds);
+      s_fwd_cols_core<A, LOGN>(io, c, l, b, tile, ar.from_u64(o[0]), ar.from_u64(o[1]), ar, tw, lds);
     }
   };
   if (mc.f64)
@@ -790,9 +784,9 @@ __global__ void __launch_bounds__(G * S2<LOGN>::CT4) ntt2s_ifwd_cols_p(NttIO io,
       for (int k = 0; k < NS; ++k)
         wa[k] = w_of<A>(pw[k]), wb[k] = w_of<A>(pw[NS + k]), wc[k] = w_of<A>(pw[2 * NS + k]);
       wl[0] = w_of<A>(pw[3 * NS]), wl[1] = w_of<A>(pw[3 * NS + 1]);
-      s_fwd_cols4_run<A, LOGN>(io, 0, c, l, b, tile, x, ar, wa, wb, wc, wl, lds + grp * REG, t);
+      s_fwd_cols4_run<A, LOGN>(io, c, l, b, tile, x, ar, wa, wb, wc, wl, lds + grp * REG, t);
     } else {
-      s_fwd_cols4_core<A, LOGN>(io, 0, c, l, b, tile, x, ar, tw, lds + grp * REG, t);
+      s_fwd_cols4_core<A, LOGN>(io, c, l, b, tile, x, ar, tw, lds + grp * REG, t);
     }
   };
   if (mc.f64)
@@ -808,29 +802,29 @@ template <int LOGN, int PRO>
 __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
     ntt2s_fwd_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::CW << S2<LOGN>::R];
-  const int job = io.job0 + blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
+  const int job = blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
   int c, l, b;
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
   if constexpr (NTT2S_R4) {
     if (mc.f64)
-      s_fwd_cols4<F64Arith, LOGN, PRO>(io, job, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds,
+      s_fwd_cols4<F64Arith, LOGN, PRO>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds,
                                        tb);
     else
-      s_fwd_cols4<IntArith, LOGN, PRO>(io, job, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds,
+      s_fwd_cols4<IntArith, LOGN, PRO>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds,
                                        tb);
   } else if (mc.f64)
-    s_fwd_cols<F64Arith, LOGN, PRO>(io, job, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds, tb);
+    s_fwd_cols<F64Arith, LOGN, PRO>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds, tb);
   else
-    s_fwd_cols<IntArith, LOGN, PRO>(io, job, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds, tb);
+    s_fwd_cols<IntArith, LOGN, PRO>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds, tb);
 }
 
 template <int LOGN, int EPI>
 __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT)
     ntt2s_fwd_rows(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::RW * 256];
-  const int job = io.job0 + blockIdx.x / S2<LOGN>::RTILES, tile = blockIdx.x % S2<LOGN>::RTILES;
+  const int job = blockIdx.x / S2<LOGN>::RTILES, tile = blockIdx.x % S2<LOGN>::RTILES;
   int c, l, b;
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
@@ -838,40 +832,40 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT)
   static_assert(NTT2S_R4 || !epi_aut(EPI), "the automorphism epilogue is radix-4 only");
   if constexpr (NTT2S_R4) {
     if (mc.f64)
-      s_fwd_rows4<F64Arith, LOGN, EPI>(io, job, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds);
+      s_fwd_rows4<F64Arith, LOGN, EPI>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds);
     else
-      s_fwd_rows4<IntArith, LOGN, EPI>(io, job, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds);
+      s_fwd_rows4<IntArith, LOGN, EPI>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds);
   } else if (mc.f64)
-    s_fwd_rows<F64Arith, LOGN, EPI>(io, job, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds);
+    s_fwd_rows<F64Arith, LOGN, EPI>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds);
   else
-    s_fwd_rows<IntArith, LOGN, EPI>(io, job, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds);
+    s_fwd_rows<IntArith, LOGN, EPI>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds);
 }
 
 template <int LOGN>
 __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT)
     ntt2s_inv_rows(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::RW * 256];
-  const int job = io.job0 + blockIdx.x / S2<LOGN>::RTILES, tile = blockIdx.x % S2<LOGN>::RTILES;
+  const int job = blockIdx.x / S2<LOGN>::RTILES, tile = blockIdx.x % S2<LOGN>::RTILES;
   int c, l, b;
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
   if constexpr (NTT2S_R4) {
     if (mc.f64)
-      s_inv_rows4<F64Arith, LOGN>(io, job, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
+      s_inv_rows4<F64Arith, LOGN>(io, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
     else
-      s_inv_rows4<IntArith, LOGN>(io, job, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
+      s_inv_rows4<IntArith, LOGN>(io, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
   } else if (mc.f64)
-    s_inv_rows<F64Arith, LOGN>(io, job, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
+    s_inv_rows<F64Arith, LOGN>(io, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
   else
-    s_inv_rows<IntArith, LOGN>(io, job, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
+    s_inv_rows<IntArith, LOGN>(io, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
 }
 
 template <int LOGN>
 __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
     ntt2s_inv_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::CW << S2<LOGN>::R];
-  const int job = io.job0 + blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
+  const int job = blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
   int c, l, b;
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
@@ -882,7 +876,7 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
       constexpr int CW = S2<LOGN>::CW, Q = 1 << (S2<LOGN>::R - 2);
       const int t = threadIdx.x, cl = t % CW, j = t / CW, col = tile * CW + cl;
       typename A::T x[4], y[4];
-      const u64* m = mid_row_s(io, job, c, l, b);
+      const u64* m = row_ptr(io.mid, c, l, b);
       s_inv_cols4_src<A, A, LOGN, false>(m, m, ar, ar, tw, tw, lds, x, y, t, tile);
       u64* dst = row_ptr(io.dst, c, l, b);
 #pragma unroll
@@ -893,9 +887,9 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
     else
       inv(IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN));
   } else if (mc.f64)
-    s_inv_cols<F64Arith, LOGN>(io, job, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
+    s_inv_cols<F64Arith, LOGN>(io, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
   else
-    s_inv_cols<IntArith, LOGN>(io, job, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
+    s_inv_cols<IntArith, LOGN>(io, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
 }
 
 template <int LOGN>
@@ -903,10 +897,7 @@ int launch2s(const NttIO& io, const DeviceTables* tb, bool inverse, bool rows_on
   const int total = io.dst.ncomp * io.dst.nlimb * io.dst.nbatch;
   if (total == 0) return 0;
   if (io.jobs != total || io.ci) return -1;
-  const int jobs = io.njob ? io.njob : total;
-  if (io.job0 < 0 || io.job0 + jobs > total) return -1;
-  if (io.mid_compact && io.mid.batch_stride < (1 << LOGN)) return -1;
-  const dim3 ga(jobs * S2<LOGN>::CTILES), ba(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT), gb(jobs * S2<LOGN>::RTILES),
+  const dim3 ga(total * S2<LOGN>::CTILES), ba(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT), gb(total * S2<LOGN>::RTILES),
       bb(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT);
   if (inverse) {
     if (io.pro != NTT_PRO_LOAD || io.epi != NTT_EPI_STORE) return -1;
@@ -917,7 +908,7 @@ int launch2s(const NttIO& io, const DeviceTables* tb, bool inverse, bool rows_on
     return 0;
   }
   if (io.ifuse && io.tgroup > 1) {
-    if (io.mid_compact || !io.imid.p || io.job0 != 0 || jobs != total || io.ntg < 1) return -1;
+    if (!io.imid.p || io.ntg < 1) return -1;
     const dim3 gg(io.dst.ncomp * io.dst.nbatch * io.ntg * S2<LOGN>::CTILES);
     if constexpr (NTT2S_R4) {
       const bool bx = io.pro == NTT_PRO_BEXT;
@@ -941,7 +932,7 @@ int launch2s(const NttIO& io, const DeviceTables* tb, bool inverse, bool rows_on
       return -1;
     }
   } else if (io.ifuse) {
-    if (io.mid_compact || !io.imid.p) return -1;
+    if (!io.imid.p) return -1;
     if (io.pro == NTT_PRO_BEXT)
       hipLaunchKernelGGL((ntt2s_ifwd_cols<LOGN, NTT_PRO_BEXT>), ga, ba, 0, st, io, tb);
     else if (io.pro == NTT_PRO_RESCALE)
@@ -980,7 +971,7 @@ int launch2s(const NttIO& io, const DeviceTables* tb, bool inverse, bool rows_on
 // inside the forward launch that reads this INTT, NttIO.ifuse)
 int orion_launch_ntt2s(int logN, const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t st,
                        bool rows_only) {
-  if (rows_only && (!inverse || io.mid_compact)) return -1;
+  if (rows_only && !inverse) return -1;
   switch (logN) {
     case 15: return launch2s<15>(io, tb, inverse, rows_only, st);
     case 16: return launch2s<16>(io, tb, inverse, rows_only, st);

@@ -37,10 +37,10 @@ __device__ __forceinline__ void sem_release(unsigned* s) {
 }
 
 __global__ void __launch_bounds__(1024) job_kernel(u64* __restrict__ buf, int nlimb, int spin, int limit,
-                                                   unsigned* sem, int stagger) {
+                                                   unsigned* sem, int delay) {
   const int t = threadIdx.x;
-  if (blockIdx.x & 8)  // the stagger alternative: half of each XCD's CUs start late
-    for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
+  if (blockIdx.x & 8)  // the late-start alternative: half of each XCD's CUs start late
+    for (int i = 0; i < delay; ++i) __builtin_amdgcn_s_sleep(127);
   unsigned* s = sem + (blockIdx.x & 7) * 64;
   u64 a[32];
   int prev = -1;
@@ -92,20 +92,20 @@ int main() {
   hipEventCreate(&e1);
   int ncu = 0;
   hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
-  auto run = [&](int G, int spin, int limit, int stagger) {
+  auto run = [&](int G, int spin, int limit, int delay) {
     for (int i = 0; i < 2; ++i)
-      hipLaunchKernelGGL(job_kernel, dim3(G), dim3(1024), 0, 0, d, nl, spin, limit, sem, stagger);
+      hipLaunchKernelGGL(job_kernel, dim3(G), dim3(1024), 0, 0, d, nl, spin, limit, sem, delay);
     hipEventRecord(e0, 0);
     const int reps = 5;
     for (int i = 0; i < reps; ++i)
-      hipLaunchKernelGGL(job_kernel, dim3(G), dim3(1024), 0, 0, d, nl, spin, limit, sem, stagger);
+      hipLaunchKernelGGL(job_kernel, dim3(G), dim3(1024), 0, 0, d, nl, spin, limit, sem, delay);
     hipEventRecord(e1, 0);
     hipEventSynchronize(e1);
     float ms;
     hipEventElapsedTime(&ms, e0, e1);
     const double us = ms * 1e3 / reps;
-    printf("G %3d spin %4d limit/XCD %3d stagger %3d : %8.1f us/launch  %6.1f us per job per CU  %6.1f us per 256 limbs  "
-           "%7.1f GB/s\n", G, spin, limit, stagger, us, us / ((double)nl / G), us / (nl / 256.0),
+    printf("G %3d spin %4d limit/XCD %3d delay %3d : %8.1f us/launch  %6.1f us per job per CU  %6.1f us per 256 limbs  "
+           "%7.1f GB/s\n", G, spin, limit, delay, us, us / ((double)nl / G), us / (nl / 256.0),
            16.0 * 32768 * nl / (us * 1e-6) / 1e9);
     fflush(stdout);
   };
@@ -114,7 +114,7 @@ int main() {
   for (int G : {8, 16, 32, 64, 128, 192, 256}) run(G, 0, 0, 0);
   for (int spin : {0, 40, 80}) {
     for (int limit : {0, 24, 16, 12, 8, 6, 4}) run(ncu, spin, limit, 0);
-    for (int stagger : {2, 5}) run(ncu, spin, 0, stagger);
+    for (int delay : {2, 5}) run(ncu, spin, 0, delay);
   }
   unsigned h[8 * 64];
   hipMemcpy(h, sem, sizeof(h), hipMemcpyDeviceToHost);

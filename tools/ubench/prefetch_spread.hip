@@ -23,15 +23,15 @@ __device__ __forceinline__ double spin_d(double d, int spin) {
 }
 
 template <int MODE>
-__global__ void __launch_bounds__(512) k_job(const u64* __restrict__ src, u64* __restrict__ dst, int njob, int spin) {
+__global__ void __launch_bounds__(512) k_job(const u64* __restrict__ src, u64* __restrict__ dst, int n_jobs, int spin) {
   const int t = threadIdx.x;
   u64 a[32], b[32];
   int job = blockIdx.x;
-  if (job >= njob) return;
+  if (job >= n_jobs) return;
 #pragma unroll
   for (int k = 0; k < 32; ++k) a[k] = src[(size_t)job * 16384 + t + 512 * k];
-  for (; job < njob; job += gridDim.x) {
-    const int next = job + gridDim.x < njob ? job + gridDim.x : job;
+  for (; job < n_jobs; job += gridDim.x) {
+    const int next = job + gridDim.x < n_jobs ? job + gridDim.x : job;
     const u64* np = src + (size_t)next * 16384 + t;
     if (MODE == 1) {
 #pragma unroll
@@ -62,20 +62,20 @@ __global__ void __launch_bounds__(512) k_job(const u64* __restrict__ src, u64* _
 }
 
 int main() {
-  const int njob = 8192;
+  const int n_jobs = 8192;
   u64 *s, *d;
-  hipMalloc(&s, (size_t)njob * 16384 * 8);
-  hipMalloc(&d, (size_t)njob * 16384 * 8);
-  hipMemset(s, 1, (size_t)njob * 16384 * 8);
+  hipMalloc(&s, (size_t)n_jobs * 16384 * 8);
+  hipMalloc(&d, (size_t)n_jobs * 16384 * 8);
+  hipMemset(s, 1, (size_t)n_jobs * 16384 * 8);
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
   for (int spin : {0, 25, 50, 100}) {
     for (int mode = 0; mode < 3; ++mode) {
       auto launch = [&]() {
-        if (mode == 0) hipLaunchKernelGGL(k_job<0>, dim3(256), dim3(512), 0, 0, s, d, njob, spin);
-        if (mode == 1) hipLaunchKernelGGL(k_job<1>, dim3(256), dim3(512), 0, 0, s, d, njob, spin);
-        if (mode == 2) hipLaunchKernelGGL(k_job<2>, dim3(256), dim3(512), 0, 0, s, d, njob, spin);
+        if (mode == 0) hipLaunchKernelGGL(k_job<0>, dim3(256), dim3(512), 0, 0, s, d, n_jobs, spin);
+        if (mode == 1) hipLaunchKernelGGL(k_job<1>, dim3(256), dim3(512), 0, 0, s, d, n_jobs, spin);
+        if (mode == 2) hipLaunchKernelGGL(k_job<2>, dim3(256), dim3(512), 0, 0, s, d, n_jobs, spin);
       };
       for (int i = 0; i < 2; ++i) launch();
       hipEventRecord(e0, 0);
@@ -86,7 +86,7 @@ int main() {
       hipEventElapsedTime(&ms, e0, e1);
       const double us = ms * 1000.0 / 5;
       printf("mode %d spin %4d : %8.1f us/launch  %6.2f us per 256 jobs  %7.1f GB/s\n", mode, spin, us,
-             us / (njob / 256.0), 2.0 * 131072.0 * njob / (us * 1e-6) / 1e9);
+             us / (n_jobs / 256.0), 2.0 * 131072.0 * n_jobs / (us * 1e-6) / 1e9);
     }
   }
   return 0;
