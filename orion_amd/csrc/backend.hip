@@ -41,6 +41,8 @@ int orion_launch_gather(u64* dst, long long d_comp, long long d_limb, int nimg, 
                         int N, hipStream_t st);
 int orion_launch_basis_ext(const LimbSet& out, const LimbSet& in, const BasisExtTable* T, const DeviceTables* tb,
                            int N, hipStream_t st);
+int orion_launch_basis_ext_rescale(const LimbSet& out, const LimbSet& in, const BextRescaleTable* W, int N,
+                                   hipStream_t st);
 int orion_launch_modup_all(const LimbSet& D, const LimbSet& in, const BasisExtTable* Ts, int beta, int K,
                            int nqp, const DeviceTables* tb, int N, hipStream_t st);
 int orion_launch_ks_mac(const LimbSet& out, const LimbSet& D, const LimbSet& own, const MacGroups& G, int ngroup,
@@ -396,6 +398,9 @@ struct Ciphertext {
   // buffer (Lattigo returns a copy, evaluator.go:92-99); the first in-place op
   // on either one, while both are alive, copies it first (Context::inplace_ct)
   std::shared_ptr<char> share;
+  // "ModDown pending" (Context::Deferred kind 3): the QP accumulator
+  // [Q 0..level][P] whose final ModDown has not run; poly has no buffer yet
+  Poly pend;
 };
 
 struct Plaintext {
@@ -472,6 +477,13 @@ class HandlePool {  // lowest-free-id reuse (minheap.go:46-64)
     static Check c = nullptr;
     return c;
   }
+  // run on every foreign object get() returns, after the hook has ordered the
+  // streams (a ciphertext whose ModDown is pending on its own context)
+  using Fix = void (*)(T&, int owner);
+  static Fix& fix() {
+    static Fix f = nullptr;
+    return f;
+  }
   int add(T&& v) {
     std::lock_guard<std::mutex> lk(mu_);
     int id;
@@ -500,6 +512,7 @@ class HandlePool {  // lowest-free-id reuse (minheap.go:46-64)
       T& v = o->get_local(id, &birth, true);
       if (check()) check()(v);
       if (hook()) hook()(own, birth);
+      if (fix()) fix()(v, own);
       if (hold()) hold()(v);
       return v;
     }
@@ -667,6 +680,7 @@ struct Context {
   std::map<std::pair<int, int>, BasisExtTable*> betab;
   std::map<std::pair<int, int>, std::vector<int>> betab_pos;  // target positions (QP order)
   std::map<int, BasisExtTable*> modup_arr;  // level -> the digits' ModUp tables, contiguous (one device array)
+  std::map<int, BextRescaleTable*> mdrs_tab;  // level -> the "ModDown, then rescale" table
 
   HandlePool<Plaintext> pts;
   HandlePool<Ciphertext> cts;
@@ -723,6 +737,7 @@ struct Context {
     for (auto& kv : autidx) hipFree(kv.second);
     for (auto& kv : betab) hipFree(kv.second);
     for (auto& kv : modup_arr) hipFree(kv.second);
+    for (auto& kv : mdrs_tab) hipFree(kv.second);
     for (auto& kv : garner) hipFree(kv.second);
     for (void* p : static_bufs) hipFree(p);
     if (d_tb) hipFree(d_tb);
@@ -931,8 +946,17 @@ struct Context {
   // (rotate_add_inplace), and r's contents are never formed.  Any other C-ABI
   // call first runs what is pending as the op-by-op path would (defer_flush
   // at the API layer).  ORION_DEFER=0 turns this and RescaleNew's aliasing off.
+  //
+  // "ModDown pending" (kind 3): EvaluateLinearTransform and
+  // MulRelinCiphertextNew return r with its level, scale and batch, holding
+  // the QP accumulator (Ciphertext::pend) instead of running the final
+  // ModDown, where moddown_rescale applies.  Rescale / RescaleNew of r as the
+  // next call runs both as one division by P q_l (moddown_rescale); any other
+  // call first runs the plain ModDown (metadata reads and deletes of other
+  // handles keep it pending); deleting r drops the work.  Another context
+  // that reads r runs the plain ModDown itself (foreign_finish).
   struct Deferred {
-    int kind = 0;  // 1: r = Rotate(x, k) pending; 2: and x += r pending
+    int kind = 0;  // 1: r = Rotate(x, k) pending; 2: and x += r pending; 3: r's ModDown pending
     int x = -1, r = -1, k = 0;
   };
   Deferred dfr;
@@ -1463,6 +1487,13 @@ struct Context {
   BasisExtTable* make_betab(const std::vector<int>& src, const std::vector<int>& dst, bool centered = false) {
     no_capture("a basis extension table");
     BasisExtTable T;
+    fill_betab(T, src, dst, centered);
+    BasisExtTable* d;
+    HIPCHK(hipMalloc(&d, sizeof(T)));
+    h2d(d, &T, sizeof(T));
+    return d;
+  }
+  void fill_betab(BasisExtTable& T, const std::vector<int>& src, const std::vector<int>& dst, bool centered) const {
     memset(&T, 0, sizeof(T));
     T.ns = (int)src.size();
     T.nt = (int)dst.size();
@@ -1504,10 +1535,6 @@ struct Context {
       pieces(R.nS, R.n0, R.n1, R.n2);
       R.mode = T.centered ? BEXT_LAZY : bext_mode(src, T.ns, tm);
     }
-    BasisExtTable* d;
-    HIPCHK(hipMalloc(&d, sizeof(T)));
-    h2d(d, &T, sizeof(T));
-    return d;
   }
   // ModUp of digit i at level: sources Q[lo,hi), targets = rest of QP in QP-position order
   BasisExtTable* modup_tab(int level, int digit, std::vector<int>& tpos) {
@@ -1556,6 +1583,37 @@ struct Context {
     for (int k = 0; k < K; ++k) src.push_back(L + k);
     BasisExtTable* d = make_betab(src, iota(0, level + 1));
     betab[key] = d;
+    return d;
+  }
+  // the ModDown table of `level` (>= 1) with the constants of the rescale by
+  // q_level folded into it (common.h BextRescaleTable)
+  BextRescaleTable* moddown_rescale_tab(int level) {
+    auto it = mdrs_tab.find(level);
+    if (it != mdrs_tab.end()) return it->second;
+    no_capture("a basis extension table");
+    if (level < 1 || level >= L) throw std::runtime_error("moddown_rescale: no such level");
+    std::vector<int> src;
+    for (int k = 0; k < K; ++k) src.push_back(L + k);
+    std::vector<BextRescaleTable> W(1);
+    memset(&W[0], 0, sizeof(BextRescaleTable));
+    fill_betab(W[0].bx, src, iota(0, level + 1), false);
+    const std::vector<u64> pq = p_mod_q(level);
+    const u64 ql = mods[level], h = ql >> 1;
+    W[0].piv = level;
+    W[0].pinv = hm_invmod(pq[level], ql);
+    W[0].pinvs = hm_shoup(W[0].pinv, ql);
+    W[0].h = h;
+    for (int i = 0; i < level; ++i) {
+      BextRescaleTarget& R = W[0].rt[i];
+      R.pq = pq[i];
+      R.pqs = hm_shoup(pq[i], mods[i]);
+      R.hm = h % mods[i];
+      R.ones = hm_shoup(1, mods[i]);
+    }
+    BextRescaleTable* d;
+    HIPCHK(hipMalloc(&d, sizeof(BextRescaleTable)));
+    h2d(d, W.data(), sizeof(BextRescaleTable));
+    mdrs_tab[level] = d;
     return d;
   }
 
@@ -2048,15 +2106,61 @@ struct Context {
     }
     if (aut_g && !scatter) automorph(out, dst, aut_g, aut_acc);
   }
+  // whether a ModDown at `level` that is rescaled next runs as moddown_rescale:
+  // where the ModDown takes the separate basis_ext route (small launches keep
+  // the fused latency path and the sequential rescale)
+  bool moddown_rescale_ok(int nc, int B, int level) {
+    return level >= 1 && K <= ORION_MAXSRC && !fuse_bext(nc * B * (level + 1), K, NTT_EPI_SUBSCALE, false);
+  }
+  // ModDown of x (as moddown's, at `level` >= 1) and the rescale of its result
+  // by q_level as one division by P q_level; out: limbs 0..level-1.  Both
+  // transforms are linear, so the two subtractions are made once, in the
+  // coefficient domain (common.h BextRescaleTable):
+  //   out_i = (x_i - NTT(e_i + (P mod q_i) t_i)) (P q_level)^-1
+  // which is the sequential result limb for limb: the float quotient is the
+  // ModDown's, everything else exact.  Clobbers x's limbs level..level+K.
+  void moddown_rescale(const LimbSet& x, int level, const LimbSet& out) {
+    const int nc = x.ncomp, B = x.nbatch, l = level;
+    if (l < 1) throw std::runtime_error("cannot rescale a level-0 ciphertext");
+    if (out.nlimb != l) throw std::runtime_error("moddown_rescale: the output has level - 1");
+    BextRescaleTable* W = moddown_rescale_tab(l);
+    LimbSet xs = limbs(x, l, K + 1);  // limb l and the P limbs: adjacent in [Q 0..l][P]
+    ntt(xs, true);
+    Poly ext = alloc(nc, l, B);
+    LimbSet le = lsq(ext, 0, nc, l - 1);
+    {
+      Scope sc(this, P_BEXT, 8.0 * N * B * nc * (K + 1 + l));
+      if (orion_launch_basis_ext_rescale(le, xs, W, N, stream))
+        throw std::runtime_error("basis_ext: unsupported source count");
+    }
+    NttIO io = nio(out, le);
+    io.epi = NTT_EPI_SUBSCALE;
+    io.ex = limbs(x, 0, l);
+    const std::vector<u64> pq = p_mod_q(l - 1);
+    for (int j = 0; j < l; ++j) {
+      io.s[j] = hm_invmod(hm_mulmod(pq[j], mods[l] % mods[j], mods[j]), mods[j]);
+      io.ss[j] = hm_shoup(io.s[j], mods[j]);
+    }
+    ntt_io(io, false);
+  }
   // full key switch of c (Q, level) -> (k0, k1) written to out comps 0/1 (Q, level);
   // add0/add1 (optional, Q limbs 0..level with out's batch geometry): added to
   // comps 0/1 of the result, folded into the gadget product as P * add; aut_g:
   // the result permuted by that Galois element's automorphism (moddown), and
   // added to out's comps 0/1 for aut_acc
   void keyswitch(const LimbSet& c, int level, int B, const Poly& key, int klvl, const Poly& out,
-                 const u64* add0 = nullptr, const u64* add1 = nullptr, u64 aut_g = 0, bool aut_acc = false) {
+                 const u64* add0 = nullptr, const u64* add1 = nullptr, u64 aut_g = 0, bool aut_acc = false,
+                 Poly* keep_qp = nullptr) {
     if (klvl < level) throw std::runtime_error("evaluation key made for a lower level");
     Poly u = alloc(2, level + 1 + K, B);
+    if (keep_qp) {  // (the caller checked moddown_rescale_ok: no fused latency path here) no ModDown
+      Poly D = decompose(c, level, B);
+      const int beta = (level + 1 + K - 1) / K;
+      mac_groups(lsqp(u, 0, 2, level, level), 0, lsqp(D, 0, beta, level, level), 0, c, 0, {key.ptr()}, {klvl}, beta,
+                 add0, 0, add0 ? level + 1 : 0, add1, 0, false);
+      *keep_qp = u;
+      return;
+    }
     // when the gadget product runs the ModDown INTT's rows pass, it can run
     // the decomposition NTT's forward rows pass too (ORION_MAC_FWD_ROWS)
     const bool rows_q = mac_fwd_rows && moddown_rows_fusable(lsqp(u, 0, 2, level, level), level,
@@ -2089,6 +2193,33 @@ struct Context {
     c.level = level;
     c.scale = scale;
     return c;
+  }
+  // a result whose final ModDown is pending: metadata now, the buffer when it runs
+  Ciphertext pending_ct(int level, int B, long double scale) {
+    Ciphertext c;
+    c.poly.B = B;
+    c.level = level;
+    c.scale = scale;
+    return c;
+  }
+  // runs the pending ModDown of r as the op-by-op path would have
+  void finish_moddown(Ciphertext& r) {
+    if (!r.pend.buf) return;
+    const int B = r.pend.B;
+    Poly o = alloc(2, r.level + 1, B);
+    moddown(lsqp(r.pend, 0, 2, r.level, r.level), r.level, lsq(o, 0, 2, r.level));
+    r.poly = o;
+    r.pend = Poly();
+  }
+  // ... or, when a rescale is what comes next, both as one division
+  void finish_moddown_rescale(Ciphertext& r) {
+    const int l = r.level, B = r.pend.B;
+    Poly o = alloc(2, l, B);
+    moddown_rescale(lsqp(r.pend, 0, 2, l, l), l, lsq(o, 0, 2, l - 1));
+    r.poly = o;
+    r.pend = Poly();
+    r.level = l - 1;
+    r.scale /= (long double)mods[l];
   }
   Ciphertext clone(const Ciphertext& a) {
     Ciphertext c = new_ct(a.level, a.poly.B, a.scale);
@@ -2150,7 +2281,8 @@ struct Context {
     throw std::runtime_error("batch size mismatch");
   }
 
-  Ciphertext mul_relin(const Ciphertext& a, const Ciphertext& b) {
+  // keep_qp: as eval_lt's
+  Ciphertext mul_relin(const Ciphertext& a, const Ciphertext& b, bool keep_qp = false) {
     if (!have_rlk) throw std::runtime_error("relinearization key not generated");
     const int level = std::min(a.level, b.level);
     const int B = batch_of(a.poly.B, b.poly.B);
@@ -2162,6 +2294,12 @@ struct Context {
       const bool square = a.poly.ptr() == b.poly.ptr();
       Scope sc(this, P_TENSOR, 8.0 * N * (level + 1) * B * (square ? 5 : 7));
       orion_launch_tensor(ld, lsq(a.poly, 0, 2, level, B), lsq(b.poly, 0, 2, level, B), d_tb, N, stream);
+    }
+    if (keep_qp && moddown_rescale_ok(2, B, level)) {
+      Ciphertext out = pending_ct(level, B, a.scale * b.scale);
+      keyswitch(lsq(d, 2, 1, level), level, B, rlk, L - 1, out.poly, d.ptr(), d.ptr() + d.comp_stride(), 0, false,
+                &out.pend);
+      return out;
     }
     Ciphertext out = new_ct(level, B, a.scale * b.scale);
     // (d0, d1) + keyswitch(d2): the addition is folded into the gadget product
@@ -2318,7 +2456,9 @@ struct Context {
   //   4. all giant key switches: ModDown of c1, decomposition, MAC with each
   //      giant's key (+ c0 folded in), then the automorphism-accumulate;
   //   5. ModDown of the accumulator.
-  Ciphertext eval_lt(LinTrans& T, const Ciphertext& ct) {
+  // keep_qp: where moddown_rescale would apply, step 5 is left out and the
+  // result holds the accumulator instead (Ciphertext::pend)
+  Ciphertext eval_lt(LinTrans& T, const Ciphertext& ct, bool keep_qp = false) {
     const int level = std::min(ct.level, T.level);
     const int B = ct.poly.B, nqp = level + 1 + K;
     const int beta = (level + 1 + K - 1) / K;
@@ -2394,11 +2534,14 @@ struct Context {
     // 4. giant key switches and the automorphism-accumulation (lt_giant)
     Poly acc = alloc(2, nqp, B);
     LimbSet la = lsqp(acc, 0, 2, level, level);
-    Ciphertext out = new_ct(level, B, ct.scale * (long double)mods[T.level]);
-    const LimbSet lo = lsq(out.poly, 0, 2, level);
+    const bool pend = keep_qp && moddown_rescale_ok(2, B, level);
+    Ciphertext out = pend ? pending_ct(level, B, ct.scale * (long double)mods[T.level])
+                          : new_ct(level, B, ct.scale * (long double)mods[T.level]);
+    const LimbSet lo = pend ? la : lsq(out.poly, 0, 2, level);
     // one lt_giant launch: it may store the P limbs through the final
     // ModDown INTT's rows pass (as keyswitch's gadget product does)
-    const bool rows = nzg > 0 && nzg <= ORION_MAXGROUP && moddown_rows_fusable(la, level, lo, 0, false);
+    const bool rows =
+        !pend && nzg > 0 && nzg <= ORION_MAXGROUP && moddown_rows_fusable(la, level, lo, 0, false);
     LimbSet z = lsqp(Tt, ng - 1, 2, level, level);  // the zero giant: (c0, c1) at comps ng-1, 2ng-1
     z.comp_stride = (long long)ng * Tt.comp_stride();
     if (nzg > 0) {
@@ -2449,7 +2592,10 @@ struct Context {
       copy(la, z);
     }
     // 5.
-    moddown(la, level, lo, 0, false, rows);
+    if (pend)
+      out.pend = acc;
+    else
+      moddown(la, level, lo, 0, false, rows);
     return out;
   }
 
@@ -3215,8 +3361,12 @@ struct Context {
     return o;
   }
   Ciphertext lt_rescale(LinTrans& T, const Ciphertext& x) {
-    Ciphertext y = eval_lt(T, x);
-    rescale_inplace(y);
+    // (the final ModDown and the rescale as one division where that applies)
+    Ciphertext y = eval_lt(T, x, defer_on);
+    if (y.pend.buf)
+      finish_moddown_rescale(y);
+    else
+      rescale_inplace(y);
     y.scale = x.scale;  // diagonals at scale q_level
     return y;
   }
@@ -3452,6 +3602,25 @@ static void foreign_order(int owner, unsigned long long birth, bool always) {
   wait_on(*me, *o);
   if (!always) me->synced[owner] = stamp;
 }
+// a ciphertext of context `owner` whose ModDown is pending there (Deferred
+// kind 3), read by the acting context: the plain ModDown runs here, on this
+// context's stream (which the hook has ordered after the owner's), into a
+// buffer of the owner's pool.  That buffer may have been released by work the
+// owner queued since, so this stream waits for the owner's once more; the
+// owner's stream then waits for the ModDown before the accumulator goes back
+// to its pool.  The owner's record stays: its flush finds nothing pending
+static void foreign_finish(Ciphertext& v, int owner) {
+  Context* me = t_act;
+  Context* o = slot_ctx(owner);
+  if (!v.pend.buf || !me || !o || o == me) return;
+  const int level = v.level;
+  Poly out = o->alloc(2, level + 1, v.pend.B);
+  wait_on(*me, *o);
+  me->moddown(me->lsqp(v.pend, 0, 2, level, level), level, me->lsq(out, 0, 2, level));
+  wait_on(*o, *me);
+  v.poly = out;
+  v.pend = Poly();
+}
 static HandlePool<Ciphertext>* res_cts(int i) { Context* c = slot_ctx(i); return c ? &c->cts : nullptr; }
 static HandlePool<Plaintext>* res_pts(int i) { Context* c = slot_ctx(i); return c ? &c->pts : nullptr; }
 static HandlePool<LinTrans>* res_lts(int i) { Context* c = slot_ctx(i); return c ? &c->lts : nullptr; }
@@ -3468,6 +3637,7 @@ static const bool g_hooks_set = [] {
   HandlePool<Ciphertext>::check() = [](const Ciphertext& c) {
     if (!c.poison.empty()) throw std::runtime_error(c.poison);
   };
+  HandlePool<Ciphertext>::fix() = foreign_finish;
   HandlePool<Ciphertext>::hold() = [](const Ciphertext& c) {
     if (t_act && t_act->capturing && c.poly.buf) t_act->capture_holds.push_back(c.poly.buf);
   };
@@ -3610,8 +3780,9 @@ static int ct_ct_op(int i0, int i1, int op, bool inplace);
 // (which the AddCiphertext already reported as done) or r fails loudly with
 // this error, instead of reading a buffer that was never written
 static void poison_deferred(Context& c, const Context::Deferred& d, const char* what) {
-  const std::string msg = std::string("a deferred rotation by ") + std::to_string(d.k) + " failed (" + what +
-                          "): this ciphertext was never written";
+  const std::string msg = (d.kind == 3 ? std::string("a deferred ModDown")
+                                       : std::string("a deferred rotation by ") + std::to_string(d.k)) +
+                          " failed (" + what + "): this ciphertext was never written";
   for (int id : {d.r, d.kind == 2 ? d.x : -1}) {
     if (id < 0) continue;
     try {
@@ -3626,6 +3797,10 @@ static void defer_flush() {
   const Context::Deferred d = c.dfr;
   c.dfr = Context::Deferred();
   try {
+    if (d.kind == 3) {
+      c.finish_moddown(c.cts.get(d.r));
+      return;
+    }
     c.rotate_into(c.cts.get(d.x), d.k, c.cts.get(d.r));
     if (d.kind == 2) ct_ct_op(d.x, d.r, EW_ADD, true);
   } catch (const std::exception& e) {
@@ -3648,6 +3823,9 @@ static bool defer_keeps(const char* fn) {
 }
 static void defer_gate(const char* fn) {
   if (!t_act || !t_act->dfr.kind) return;
+  // a pending ModDown is matched by Rescale / RescaleNew, which run it
+  // themselves when they name another handle (as AddCiphertext does)
+  if (t_act->dfr.kind == 3 && (!strcmp(fn, "Rescale") || !strcmp(fn, "RescaleNew"))) return;
   if (!defer_keeps(fn)) defer_flush();
 }
 // a call acting on the calling thread's context
@@ -3900,7 +4078,9 @@ void DeleteCiphertext(int id) {
   API_BEGIN_HANDLE(id)
   Context& c = ctx();
   const Context::Deferred d = c.dfr;
-  if (d.kind && id == d.r) {
+  if (d.kind == 3) {
+    if (id == d.r) c.dfr = Context::Deferred();  // dies unread: the ModDown never runs
+  } else if (d.kind && id == d.r) {
     c.dfr = Context::Deferred();
     // the rotation dies unread: kind 1 needs no work at all; kind 2 is
     // x += Rotate(x, k) with the addition in the key switch's store.  The
@@ -4292,18 +4472,42 @@ int OrionHipRotateAdd(int id, int k) {
   return id;
   API_END(-1)
 }
+// Rescale / RescaleNew of handle id: when its ModDown is what is pending
+// (Context::Deferred kind 3), both run as one division by P q_l
+static Ciphertext& rescale_handle(Context& c, int id) {
+  const Context::Deferred d = c.dfr;
+  if (d.kind != 3 || d.r != id) {
+    defer_flush();
+    Ciphertext& a = c.inplace_ct(id);
+    c.rescale_inplace(a);
+    return a;
+  }
+  // (a refused in-place op leaves the ModDown pending: the next call runs it)
+  Ciphertext& a = c.inplace_ct(id);
+  c.dfr = Context::Deferred();
+  if (!a.pend.buf) {  // another context read it, and ran the ModDown
+    c.rescale_inplace(a);
+    return a;
+  }
+  try {
+    c.finish_moddown_rescale(a);
+  } catch (const std::exception& e) {
+    poison_deferred(c, d, e.what());
+    throw;
+  }
+  return a;
+}
 int Rescale(int id) {
   API_BEGIN
   Context& c = ctx();
-  c.rescale_inplace(c.inplace_ct(id));
+  rescale_handle(c, id);
   return id;
   API_END(-1)
 }
 int RescaleNew(int id) {  // evaluator.go:92-99: rescales the input in place, returns a copy
   API_BEGIN
   Context& c = ctx();
-  Ciphertext& a = c.inplace_ct(id);
-  c.rescale_inplace(a);
+  Ciphertext& a = rescale_handle(c, id);
   return c.cts.add(c.alias(a));  // copy-on-write: the copy is made only if both are later written
   API_END(-1)
 }
@@ -4521,7 +4725,11 @@ int MulRelinCiphertext(int a, int b) {
 int MulRelinCiphertextNew(int a, int b) {
   API_BEGIN
   Context& c = ctx();
-  return c.cts.add(c.mul_relin(c.cts.get(a), c.cts.get(b)));
+  Ciphertext r = c.mul_relin(c.cts.get(a), c.cts.get(b), c.defer_on);
+  const bool pend = (bool)r.pend.buf;
+  const int rid = c.cts.add(std::move(r));
+  if (pend) c.dfr = Context::Deferred{3, -1, rid, 0};
+  return rid;
   API_END(-1)
 }
 
@@ -4617,7 +4825,11 @@ int EvaluateLinearTransform(int tid, int cid) {
     std::lock_guard<std::recursive_mutex> lk(o->mu);
     if (T.plan_dirty) o->build_plan(T);
   }
-  return c.cts.add(c.eval_lt(T, c.cts.get(cid)));
+  Ciphertext r = c.eval_lt(T, c.cts.get(cid), c.defer_on);
+  const bool pend = (bool)r.pend.buf;
+  const int rid = c.cts.add(std::move(r));
+  if (pend) c.dfr = Context::Deferred{3, -1, rid, 0};
+  return rid;
   API_END(-1)
 }
 void DeleteLinearTransform(int id) {

@@ -218,6 +218,26 @@ struct BasisExtTable {
   double qf[ORION_MAXSRC];      // (double)s_i (rounded, as Lattigo's float64(Q[i]))
   BextTarget tgt[ORION_MAXLIMB];
 };
+// "ModDown, then rescale" as one division by P q_l (basis_ext_rescale_kernel):
+// the ModDown table of level l (sources P, targets q_0..q_l) and, beside it,
+// the constants that fold the rescale's pivot into the extension.  With e_j the
+// extension of [x]_P to q_j and x_l limb l of x in the coefficient domain,
+//   r   = ((x_l - e_l) P^-1 + h) mod q_l,  h = q_l >> 1   (the rescale's last + h)
+//   t_i = (r mod q_i) - (h mod q_i)  mod q_i               (NTT_PRO_RESCALE's prep)
+//   out_i = e_i + (P mod q_i) t_i    mod q_i,  i < l
+// so that (x_i - NTT(out_i)) (P q_l)^-1 is the rescaled ModDown, limb for limb
+struct BextRescaleTarget {
+  u64 pq, pqs;  // P mod q_i and its Shoup companion
+  u64 hm;       // h mod q_i
+  u64 ones;     // floor(2^64 / q_i): the Shoup companion of 1 (r mod q_i for any r < 2^64)
+};
+struct BextRescaleTable {
+  BasisExtTable bx;
+  int piv, pad;      // l: the pivot's target index in bx
+  u64 pinv, pinvs;   // P^-1 mod q_l and its Shoup companion
+  u64 h;             // q_l >> 1
+  BextRescaleTarget rt[ORION_MAXLIMB];
+};
 
 // ---------------------------------------------------------------------------
 // grouped launches (one launch for many independent key switches / rotations)

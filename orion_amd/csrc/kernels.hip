@@ -240,6 +240,53 @@ __global__ void __launch_bounds__(256) basis_ext_kernel(LimbSet out, LimbSet in,
   }
 }
 
+// The ModDown's extension with the rescale that follows it folded in (common.h
+// BextRescaleTable).  in: limb 0 = limb l of x, limbs 1..ns = its P limbs, all
+// in the coefficient domain; out: the l limbs e_i + (P mod q_i) t_i.  y, v and
+// every e_j are formed as basis_ext_kernel forms them; the pivot e_l stays in
+// registers (each target chunk forms it again: one more target per chunk).
+template <int MS>
+__global__ void __launch_bounds__(256) basis_ext_rescale_kernel(LimbSet out, LimbSet in,
+                                                                const BextRescaleTable* __restrict__ W, int N,
+                                                                int tchunk) {
+  const int row = blockIdx.y;  // (comp, image)
+  const int bi = row % out.nbatch;
+  const int c = row / out.nbatch;
+  const int n = (blockIdx.x * kBlk + threadIdx.x) * 2;
+  if (n >= N) return;
+  const BasisExtTable* __restrict__ T = &W->bx;
+  const int ns = T->ns, piv = W->piv;
+  u64 x0[MS], x1[MS], y0[MS], y1[MS];
+#pragma unroll
+  for (int i = 0; i < MS; ++i) {
+    if (i >= ns) break;
+    const ulonglong2 v = *(const ulonglong2*)(in.p + row_off(in, c, 1 + i, bi) + n);
+    x0[i] = v.x;
+    x1[i] = v.y;
+  }
+  const u64 v0 = bext_prep<MS>(T, x0, y0), v1 = bext_prep<MS>(T, x1, y1);
+  u64 r0, r1;
+  {
+    const ulonglong2 xl = *(const ulonglong2*)(in.p + row_off(in, c, 0, bi) + n);
+    const u64 ql = T->tgt[piv].q, pinv = W->pinv, pinvs = W->pinvs, h = W->h;
+    u64 e0, e1;
+    bext_target2<MS>(T->tgt + piv, ns, y0, v0, y1, v1, e0, e1);
+    r0 = add_mod(shoup_mul(sub_mod(xl.x, e0, ql), pinv, pinvs, ql), h, ql);
+    r1 = add_mod(shoup_mul(sub_mod(xl.y, e1, ql), pinv, pinvs, ql), h, ql);
+  }
+  const int tend = min(piv, (int)(blockIdx.z + 1) * tchunk);
+  for (int t = blockIdx.z * tchunk; t < tend; ++t) {
+    u64 o0, o1;
+    bext_target2<MS>(T->tgt + t, ns, y0, v0, y1, v1, o0, o1);
+    const BextRescaleTarget* __restrict__ R = W->rt + t;
+    const u64 q = T->tgt[t].q, pq = R->pq, pqs = R->pqs, hm = R->hm, ones = R->ones;
+    const u64 t0 = sub_mod(shoup_mul(r0, 1, ones, q), hm, q), t1 = sub_mod(shoup_mul(r1, 1, ones, q), hm, q);
+    o0 = add_mod(o0, shoup_mul(t0, pq, pqs, q), q);
+    o1 = add_mod(o1, shoup_mul(t1, pq, pqs, q), q);
+    *(ulonglong2*)(out.p + row_off(out, c, t, bi) + n) = make_ulonglong2(o0, o1);
+  }
+}
+
 // ModUp of every digit of a decomposition in one launch (small launches:
 // one image at N = 2^13..2^15 gives a per-digit basis_ext only 16..64
 // workgroups).  Row = (comp c, digit i, image); blockIdx.z = a chunk of the
@@ -1058,6 +1105,26 @@ int orion_launch_basis_ext(const LimbSet& out, const LimbSet& in, const BasisExt
     hipLaunchKernelGGL(basis_ext_kernel<4>, g, dim3(256), 0, st, out, in, T, N, tc);
   else if (in.nlimb <= ORION_MAXSRC)
     hipLaunchKernelGGL(basis_ext_kernel<ORION_MAXSRC>, g, dim3(256), 0, st, out, in, T, N, tc);
+  else
+    return -1;
+  return 0;
+}
+
+// in: limb l of x, then the table's ns P limbs; out: the l limbs below the pivot
+int orion_launch_basis_ext_rescale(const LimbSet& out, const LimbSet& in, const BextRescaleTable* W, int N,
+                                   hipStream_t st) {
+  const int rows = out.ncomp * out.nbatch, ns = in.nlimb - 1;
+  if (out.nlimb < 1 || ns < 1 || in.ncomp != out.ncomp || in.nbatch != out.nbatch) return -1;
+  dim3 g = ew_grid(N, rows);
+  const int nt = out.nlimb;
+  g.z = target_chunks(g, nt);
+  const int tc = (nt + g.z - 1) / g.z;
+  if (ns <= 2)
+    hipLaunchKernelGGL(basis_ext_rescale_kernel<2>, g, dim3(256), 0, st, out, in, W, N, tc);
+  else if (ns <= 4)
+    hipLaunchKernelGGL(basis_ext_rescale_kernel<4>, g, dim3(256), 0, st, out, in, W, N, tc);
+  else if (ns <= ORION_MAXSRC)
+    hipLaunchKernelGGL(basis_ext_rescale_kernel<ORION_MAXSRC>, g, dim3(256), 0, st, out, in, W, N, tc);
   else
     return -1;
   return 0;

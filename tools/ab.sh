@@ -9,6 +9,7 @@
 #   PARITY [1]  GPU parity subset on the variant (NTT, key switch, LT, replays)
 #   NTT    [1]  tools/ntt_bench.py (JOBS [256,1024,4096], KINDS [f64,int,mix])
 #   BENCH  [2]  LoLA bench.py repetitions (no CPU baseline, no extras)
+#   DRIVER [0]  repetitions of the plain command `bench.py --gpus 1 --steps 20 --warmup 5`
 #   RESNET [0]  ResNet-20 N=2^16 batch 1 (tools/resnet_bench.py)
 #   KPROF  [0]  rocprofv3 --kernel-trace --stats of one short bench per variant
 # Output: gpurun_out/ab_<TAG>_* and one summary line per run on stdout.
@@ -45,6 +46,13 @@ for rep in $(seq 1 ${BENCH:-2}); do
   for v in "$@"; do
     run_env $v timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extras > ${O}_bench_${v}_$rep.log 2>&1 || { echo "bench $v failed"; tail -20 ${O}_bench_${v}_$rep.log; exit 1; }
     echo "$v bench $rep: $(summ ${O}_bench_${v}_$rep.log)"
+  done
+done
+psumm() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(d['value'], 'img/s', d['ms_per_step'], 'ms/step')" "$1"; }
+for rep in $(seq 1 ${DRIVER:-0}); do
+  for v in "$@"; do
+    run_env $v timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > ${O}_driver_${v}_$rep.log 2>&1 || { echo "driver bench $v failed"; tail -20 ${O}_driver_${v}_$rep.log; exit 1; }
+    echo "$v driver $rep: $(psumm ${O}_driver_${v}_$rep.log)"
   done
 done
 if [ "${RESNET:-0}" = 1 ]; then

@@ -8,7 +8,7 @@ rm -rf $D && mkdir -p $D
 git archive $C orion_amd/csrc include | tar -x -C $D
 OUT=orion_amd/_build/liborion_hip_$NAME.so
 OBJS=""
-for s in ntt.hip ntt2.hip kernels.hip encoder.hip backend.hip hostmath.cpp wire.cpp; do
+for s in ntt.hip ntt2.hip ntt2s.hip kernels.hip encoder.hip backend.hip hostmath.cpp wire.cpp; do
   A=""; case $s in *.hip) A=--offload-arch=gfx950;; esac
   /opt/rocm/bin/hipcc $A -O3 -fPIC -std=c++17 -ffp-contract=off -w -c $D/orion_amd/csrc/$s -o $D/$s.o &
   OBJS="$OBJS $D/$s.o"
