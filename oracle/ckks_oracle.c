@@ -949,28 +949,55 @@ void oracle_encode(const oracle_ctx *c, const double *values, int nvals, double 
   free(roots);
 }
 
-/* centered CRT reconstruction of one coefficient -> double (tests only) */
-static double crt_centered_double(const oracle_ctx *c, int level, const u64 *res) {
-  /* mixed-radix (Garner) digits, then evaluate in long double with the
-   * centered correction x - Q when x > Q/2 (decided on the top digit). */
+/* the exact integer sum_i d_i q_0 .. q_{i-1} (mixed-radix digits d) as one
+ * correctly rounded double: Lattigo decodes through
+ * new(big.Float).SetInt(x).Float64(), exact then rounded to nearest even
+ * once.  Little-endian words by Horner from the top digit; of more than one
+ * word, the top 64 bits with everything below them folded into the lowest
+ * bit (a sticky bit, 10 places under a double's rounding position, so the
+ * conversion rounds as the whole integer would). */
+static double digits_to_double(const oracle_ctx *c, int nl, const u64 *d) {
+  u64 w[MAXMOD + 1];
+  int nw = 1, top = nl - 1;
+  while (top > 0 && d[top] == 0) top--;
+  w[0] = d[top];
+  for (int j = top - 1; j >= 0; j--) {
+    u64 carry = d[j];
+    for (int t = 0; t < nw; t++) {
+      u128 p = (u128)w[t] * c->mod[j] + carry;
+      w[t] = (u64)p;
+      carry = (u64)(p >> 64);
+    }
+    if (carry) w[nw++] = carry;
+  }
+  if (nw == 1) return (double)w[0];
+  const int lz = __builtin_clzll(w[nw - 1]);
+  u64 m = w[nw - 1], rest = w[nw - 2];
+  if (lz) {
+    m = (m << lz) | (rest >> (64 - lz));
+    rest <<= lz;
+  }
+  int sticky = rest != 0;
+  for (int t = 0; t < nw - 2; t++) sticky |= w[t] != 0;
+  return ldexp((double)(m | (u64)sticky), 64 * (nw - 1) - lz);
+}
+
+/* centered CRT reconstruction of one coefficient -> double (tests only);
+ * ginv[i * nl + k] = (q_k mod q_i)^-1 mod q_i, k < i */
+static double crt_centered_double(const oracle_ctx *c, int level, const u64 *res, const u64 *ginv) {
+  /* mixed-radix (Garner) digits, the centered correction x - Q when
+   * x > (Q - 1) / 2 (decided exactly, digit by digit), then the value */
   int nl = level + 1;
   u64 d[MAXMOD];
   for (int i = 0; i < nl; i++) {
     u64 qi = c->mod[i];
     u64 x = res[i] % qi;
-    for (int k = 0; k < i; k++) {
-      u64 qk = c->mod[k] % qi;
-      x = mulmod(submod(x, d[k] % qi, qi), invmod(qk, qi), qi);
-    }
+    for (int k = 0; k < i; k++) x = mulmod(submod(x, d[k] % qi, qi), ginv[i * nl + k], qi);
     d[i] = x;
   }
-  /* value = d0 + d1 q0 + d2 q0 q1 + ...; compare with Q/2 via the mixed-radix
-   * digits of Q-1 halved: x > Q/2  <=>  x >= ceil(Q/2).  Use long double for
-   * the magnitude, exact sign decision through digit comparison. */
-  /* half digits of (Q-1)/2 in mixed radix */
+  /* the mixed-radix digits of (Q - 1) / 2: those of Q - 1 are q_i - 1; halve from the top */
   u64 h[MAXMOD];
   {
-    /* (Q-1) digits are (q_i - 1); divide by 2 from the top */
     u64 rem = 0;
     for (int i = nl - 1; i >= 0; i--) {
       u128 cur = (u128)rem * c->mod[i] + (c->mod[i] - 1);
@@ -985,30 +1012,18 @@ static double crt_centered_double(const oracle_ctx *c, int level, const u64 *res
       break;
     }
   }
-  long double val = 0.0L, base = 1.0L;
-  if (!greater) {
-    for (int i = 0; i < nl; i++) {
-      val += (long double)d[i] * base;
-      base *= (long double)c->mod[i];
+  if (!greater) return digits_to_double(c, nl, d);
+  /* Q - x with mixed radix borrow arithmetic: digits of (Q-1-x) + 1 */
+  u64 e[MAXMOD];
+  for (int i = 0; i < nl; i++) e[i] = c->mod[i] - 1 - d[i];
+  for (int i = 0; i < nl; i++) {
+    if (e[i] + 1 < c->mod[i]) {
+      e[i] += 1;
+      break;
     }
-  } else {
-    /* Q - x with mixed radix borrow arithmetic: digits of (Q-1-x) + 1 */
-    u64 e[MAXMOD];
-    for (int i = 0; i < nl; i++) e[i] = c->mod[i] - 1 - d[i];
-    for (int i = 0; i < nl; i++) {
-      if (e[i] + 1 < c->mod[i]) {
-        e[i] += 1;
-        break;
-      }
-      e[i] = 0;
-    }
-    for (int i = 0; i < nl; i++) {
-      val += (long double)e[i] * base;
-      base *= (long double)c->mod[i];
-    }
-    val = -val;
+    e[i] = 0;
   }
-  return (double)val;
+  return -digits_to_double(c, nl, e);
 }
 
 void oracle_decode(const oracle_ctx *c, int level, const u64 *pt, double scale,
@@ -1022,9 +1037,12 @@ void oracle_decode(const oracle_ctx *c, int level, const u64 *pt, double scale,
   special_tables(n, M, &rot, &roots);
   cplx *v = (cplx *)calloc(n, sizeof(cplx));
   u64 res[MAXMOD];
+  u64 *ginv = (u64 *)calloc((size_t)nl * nl, sizeof(u64));
+  for (int j = 0; j < nl; j++)
+    for (int k = 0; k < j; k++) ginv[j * nl + k] = invmod(c->mod[k] % c->mod[j], c->mod[j]);
   for (int i = 0; i < N; i++) {
     for (int j = 0; j < nl; j++) res[j] = x[(size_t)j * N + i];
-    double f = crt_centered_double(c, level, res) / scale;
+    double f = crt_centered_double(c, level, res, ginv) / scale;
     if (c->ci) { /* slot input c_j = a_j - i a_{N-j} (c_0 = a_0) */
       v[i].re = f;
       if (i) v[N - i].im = -f;
@@ -1036,6 +1054,7 @@ void oracle_decode(const oracle_ctx *c, int level, const u64 *pt, double scale,
   }
   special_fft(v, n, M, rot, roots);
   for (int i = 0; i < n; i++) values[i] = v[i].re;
+  free(ginv);
   free(x);
   free(v);
   free(rot);

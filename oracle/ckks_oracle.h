@@ -125,7 +125,9 @@ int oracle_find_best_bsgs_n1(const int *diag_idx, int ndiag, int slots,
  * listed in mods (NTT domain). */
 void oracle_encode(const oracle_ctx *ctx, const double *values, int nvals,
                    double scale, const int *mods, int nmods, uint64_t *out);
-/* Decode a [level+1][N] NTT plaintext at scale: writes N/2 reals. */
+/* Decode a [level+1][N] NTT plaintext at scale: writes N/2 reals.  Each
+ * coefficient is the exact centered integer, rounded to double once (Lattigo:
+ * big.Float.SetInt(x).Float64()), then divided by scale. */
 void oracle_decode(const oracle_ctx *ctx, int level, const uint64_t *pt,
                    double scale, double *values);
 

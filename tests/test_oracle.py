@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.helpers import PLANT_CHAINS, constant_rows, decode_edge_values, digit_limbs, plant_digit_values
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -516,3 +518,187 @@ def test_oracle_bootstrap_functional(oracle_mod, sparse):
     err = np.abs(dec - exp)
     print("oracle bootstrap error max %.3g mean %.3g" % (err.max(), err.mean()))
     assert err.max() < 1e-7 and err.mean() < 2e-8, (err.max(), err.mean())  # measured 2.1e-8 / 4.6e-9, sparse 3.0e-8 / 7.7e-9
+
+
+# ---- planted rounding-edge inputs: the CPU guards of test_gpu_bext_planted.py
+# and test_gpu_decode_planted.py (the reference checked on exactly the inputs
+# the GPU parity tests plant) ----
+
+PLANT_N = 1 << 10  # a coefficient's basis extension does not depend on the degree
+PLANT_CASES = [(name, lvl) for name, p in PLANT_CHAINS.items() for lvl in p["levels"]]
+
+
+def _plant_oracle(oracle_mod, name):
+    """the chain's primes (made for its own degree) under an oracle of degree PLANT_N"""
+    p = PLANT_CHAINS[name]
+    mods = oracle_mod.gen_moduli(p["logn"], p["logq"], p["logp"])
+    return oracle_mod.Oracle(PLANT_N.bit_length() - 1, mods, len(p["logq"]), len(p["logp"])), mods
+
+
+def _bext_restated(s, ts, x, centred):
+    """Lattigo's ModUpExact of x [len(s)][n] (sources s, targets ts) in Python
+    integers, the quotient in numpy float64: correctly rounded divisions
+    accumulated in source order, truncated.  A one-prime centred digit extends
+    x - s for x >= s >> 1.  Returns (out [len(ts)][n], quotients [len(s)][n])."""
+    n = x.shape[1]
+    S = 1
+    for si in s:
+        S *= si
+    if centred and len(s) == 1:
+        y = [[int(a) for a in x[0]]]
+        quo = np.zeros((1, n))
+        v = [int(a >= s[0] >> 1) for a in y[0]]
+    else:
+        y, quo = [], np.zeros((len(s), n))
+        for i, si in enumerate(s):
+            inv = pow(S // si, -1, si)
+            y.append([int(a) * inv % si for a in x[i]])
+            quo[i] = np.array(y[i], dtype=np.uint64).astype(np.float64) / np.float64(si)
+        vf = np.zeros(n)
+        for i in range(len(s)):
+            vf = vf + quo[i]
+        v = [int(a) for a in vf]
+    out = np.zeros((len(ts), n), dtype=np.uint64)
+    for k, t in enumerate(ts):
+        qh = [S // si % t for si in s]
+        out[k] = [(sum(y[i][c] * qh[i] for i in range(len(s))) - v[c] * S) % t for c in range(n)]
+    return out, quo
+
+
+def _quotient_sensitive(quo):
+    """per coefficient: does moving any one quotient by one ulp change trunc(sum)?"""
+    def tsum(q):
+        vf = np.zeros(q.shape[1])
+        for row in q:
+            vf = vf + row
+        return np.trunc(vf)
+
+    base = tsum(quo)
+    sens = np.zeros(quo.shape[1], dtype=bool)
+    for i in range(quo.shape[0]):
+        for to in (-np.inf, np.inf):
+            q2 = quo.copy()
+            q2[i] = np.nextafter(quo[i], to)
+            sens |= tsum(q2) != base
+    return sens
+
+
+@pytest.mark.parametrize("name,level", PLANT_CASES)
+def test_planted_modup_matches_restatement(oracle_mod, name, level):
+    """plant_digit_values' limbs through orc.modup_digit, digit by digit onto
+    every other QP modulus of the level, equal the big-integer / float64
+    restatement; the planting is what it says (3/4 of a multi-limb digit's
+    coefficients within 2^50 of 0 or S, limbs = X mod q_j); and on at least a
+    quarter of those coefficients a one-ulp move of one quotient changes the
+    truncated sum (measured 0.45-0.74 on X = delta and X = S - 1 - delta alone,
+    0 of 4000 on uniformly random X): the parity tests on these inputs tell a
+    correctly rounded quotient from a nearly right one."""
+    orc, mods = _plant_oracle(oracle_mod, name)
+    K = orc.K
+    rng = np.random.default_rng(1000 + level)
+    w, X = plant_digit_values(rng, mods, level, K, PLANT_N)
+    assert w.shape == (level + 1, PLANT_N) and w.dtype == np.uint64
+    for i, limbs in enumerate(digit_limbs(level, K)):
+        s = [mods[j] for j in limbs]
+        S = int(np.prod([int(v) for v in s], dtype=object))
+        for j in limbs:
+            assert [int(a) for a in w[j]] == [x % mods[j] for x in X[i]]
+        dst = [m for m in orc.qp_mods(level) if m not in limbs]
+        got = orc.modup_digit(w[limbs[0]:limbs[-1] + 1], limbs, dst)
+        ref, quo = _bext_restated(s, [mods[m] for m in dst], w[limbs[0]:limbs[-1] + 1], True)
+        assert np.array_equal(got, ref), (name, level, i)
+        if len(limbs) == 1:
+            half = s[0] >> 1
+            assert {0, 1, half - 1, half, half + 1, s[0] - 1} <= set(X[i])
+            continue
+        near = sum(1 for x in X[i] if min(x, S - 1 - x) < 1 << 50)
+        assert near >= 3 * PLANT_N // 4, (name, level, i, near)
+        share = _quotient_sensitive(quo).mean()
+        print(f"{name} level {level} digit {i} ({len(limbs)} limbs): quotient-sensitive share {share:.3f}")
+        assert share >= 0.25, (name, level, i, share)
+
+
+def _unit_key_moddown_sources(oracle_mod, name, level):
+    """(oracle, planted integers of digit 0, S_0, the ModDown's sources [K][n]):
+    the unit Galois key (digit 0, component 0 = 1; all else 0) makes the gadget
+    product's accumulator the ModUp of digit 0 of the planted c1; the ModDown's
+    sources are the INTT of its P limbs"""
+    orc, mods = _plant_oracle(oracle_mod, name)
+    L, K = orc.L, orc.K
+    w, X = plant_digit_values(np.random.default_rng(2000 + level), mods, level, K, PLANT_N)
+    c1 = np.stack([orc.ntt(j, w[j]) for j in range(level + 1)])
+    key = np.zeros((orc.dnum, 2, L + K, PLANT_N), dtype=np.uint64)
+    key[0, 0] = 1
+    u0, u1 = orc.gadget_product_lazy(c1, key, level)
+    assert not u1.any()
+    xp = np.stack([orc.intt(L + k, u0[level + 1 + k]) for k in range(K)])
+    S0 = int(np.prod([mods[j] for j in digit_limbs(level, K)[0]], dtype=object))
+    return orc, X[0], S0, xp
+
+
+def _near_zero_mod_p(orc, xp):
+    small = np.ones(xp.shape[1], dtype=bool)
+    for k in range(orc.K):
+        p = orc.moduli[orc.L + k]
+        small &= np.array([min(int(a), p - int(a)) <= 1 << 51 for a in xp[k]])
+    return small
+
+
+def test_planted_unit_key_plants_the_moddown(oracle_mod):
+    """SMALL at level 5: the ModDown's sources under the unit key are the
+    planted integers again.  Of the coefficients planted within 2^51 of 0 or of
+    S_0 (3/4 of all: one in eight is the uniformly random control and one in
+    eight sits on a target's edge, neither near 0, so no share of all
+    coefficients can reach 7/8), at least 90 % arrive within 2^51 of 0 mod
+    both p.  Measured 0.93: 0.99 of X = delta, 0.86 of X = S_0 - 1 - delta (a
+    near-S_0 value whose float quotient is the exact floor arrives as X, one
+    whose quotient is one high as -(1 + delta))."""
+    orc, X0, S0, xp = _unit_key_moddown_sources(oracle_mod, "small", 5)
+    planted = np.array([min(x, S0 - x) <= 1 << 51 for x in X0])
+    small = _near_zero_mod_p(orc, xp)
+    share = (small & planted).sum() / planted.sum()
+    print(f"planted {planted.mean():.3f}, of which arrive {share:.3f}; of all {small.mean():.3f}")
+    assert planted.mean() >= 0.75
+    assert share >= 0.90, share
+
+
+@pytest.mark.parametrize("name,level", [("small", 5), ("small", 1), ("k8", 16), ("n15", 5)])
+def test_planted_moddown_matches_restatement(oracle_mod, name, level):
+    """Every chain and level of the planted ModDown tests: on the sources the
+    unit key leaves, orc.basis_extend (the ModDown's extension P -> Q) equals
+    the big-integer / float64 restatement, and a one-ulp move of one quotient
+    changes the truncated sum on at least a quarter of the coefficients (the
+    condition of test_planted_modup_matches_restatement: with eight 61-bit
+    sources only 0.87 of the planted values arrive near 0 mod p -- their
+    float quotient truncates one low more often -- but the sum still sits on
+    an integer)."""
+    orc, X0, S0, xp = _unit_key_moddown_sources(oracle_mod, name, level)
+    L, K, mods = orc.L, orc.K, orc.moduli
+    src, dst = [L + k for k in range(K)], list(range(level + 1))
+    ref, quo = _bext_restated([mods[m] for m in src], [mods[m] for m in dst], xp, False)
+    assert np.array_equal(orc.basis_extend(xp, src, dst), ref)
+    share = _quotient_sensitive(quo).mean()
+    print(f"{name} level {level}: near 0 mod p {_near_zero_mod_p(orc, xp).mean():.3f}, quotient-sensitive {share:.3f}")
+    assert share >= 0.25, share
+
+
+@pytest.mark.parametrize("name,level,ci", [("small", 0, False), ("small", 1, False), ("small", 3, False),
+                                           ("small", 5, False), ("small", 3, True), ("k8", 16, False)])
+def test_decode_of_constant_is_the_rounded_integer(oracle_mod, name, level, ci):
+    """The NTT of the constant polynomial X is the constant row X mod q_j, and
+    every slot of its decoding is float(X centred) / scale exactly: one
+    correctly rounded conversion of the exact integer (Lattigo:
+    big.Float.SetInt(x).Float64(), then / scale); the special FFT of a lone
+    coefficient 0 only adds zeros.  X on the edges of the CRT, the conversion
+    and the centring (helpers.decode_edge_values)."""
+    p = PLANT_CHAINS[name]
+    mods = oracle_mod.gen_moduli(p["logn"] + ci, p["logq"], p["logp"])
+    orc = oracle_mod.Oracle(7, mods, len(p["logq"]), len(p["logp"]), ci=ci)
+    qs = mods[:level + 1]
+    sp, sweep = decode_edge_values(np.random.default_rng(3000 + level), qs)
+    xs = sp + sweep
+    rows = constant_rows(xs, qs, orc.N)
+    for scale in (2.0 ** 40, 3 * 2.0 ** 38):
+        for b, x in enumerate(xs):
+            got = orc.decode(rows[b], level, scale)
+            assert got.shape == (orc.slots,) and np.all(got == float(x) / scale), (x, scale, got[0])
