@@ -25,6 +25,7 @@
 #include "../../include/orion_hip.h"
 #include "common.h"
 #include "hostmath.h"
+#include "ntt_route.h"
 #include "wire.h"
 
 int orion_launch_ntt(int logN, const LimbSet& s, const DeviceTables* tb, bool inverse, hipStream_t st);
@@ -926,7 +927,7 @@ struct Context {
   // RescaleNew's result: a second handle on a's (just rescaled) buffer, when
   // nothing else (a captured graph) holds that buffer
   Ciphertext alias(Ciphertext& a) {
-    if (!defer_on || !a.poly.buf || a.poly.buf.use_count() != 1) return clone(a);
+    if (!tun.defer || !a.poly.buf || a.poly.buf.use_count() != 1) return clone(a);
     if (!a.share) a.share = std::make_shared<char>(0);
     Ciphertext y;
     y.poly = a.poly;
@@ -960,7 +961,6 @@ struct Context {
     int x = -1, r = -1, k = 0;
   };
   Deferred dfr;
-  bool defer_on = getenv("ORION_DEFER") ? atoi(getenv("ORION_DEFER")) != 0 : true;
 
   // lazily built tables, keys and host transfers synchronise, which would
   // invalidate an open capture (and leave HIP's stream state unusable): refuse
@@ -1051,56 +1051,11 @@ struct Context {
 #define ORION_NTT_DEFAULT_ORDER 2
 #endif
   int ntt_order = getenv("ORION_NTT_ORDER") ? atoi(getenv("ORION_NTT_ORDER")) : ORION_NTT_DEFAULT_ORDER;
-#ifndef ORION_NTT_DEFAULT_IMPL
-#define ORION_NTT_DEFAULT_IMPL 1
-#endif
-  // 1: one limb per workgroup (ntt.hip); 2: two-pass N = 2^15 kernels (ntt2.hip)
-  int ntt_impl = getenv("ORION_NTT_IMPL") ? atoi(getenv("ORION_NTT_IMPL")) : ORION_NTT_DEFAULT_IMPL;
-  // N = 2^15 launches with fewer limb-transforms than this use the two-pass
-  // kernels: one limb per CU leaves most of the 256 CUs idle there (8 jobs:
-  // 15 vs 37 us; 64 jobs: 32 vs 40 us, float64 path).  Batched launches
-  // (>= 128 jobs at 64 images) keep the one-pass kernel.
-  int ntt2_below = getenv("ORION_NTT2_BELOW") ? atoi(getenv("ORION_NTT2_BELOW")) : 128;
-  // two-pass launches of at most this many limb-transforms use the
-  // latency-oriented kernels of ntt2s.hip (one butterfly per thread per
-  // stage, the tile in LDS) instead of ntt2.hip's 16-point threads
-  int ntt2s_below = getenv("ORION_NTT2S_BELOW") ? atoi(getenv("ORION_NTT2S_BELOW")) : 128;
-  // decompositions with fewer limb-transforms per digit than this run every
-  // digit's ModUp + NTT as one launch pair (0 = always per digit)
-  int modup_merge = getenv("ORION_MODUP_MERGE") ? atoi(getenv("ORION_MODUP_MERGE")) : 256;
-  // 1: ModUp and ModDown form the extended limbs in the forward NTT's prologue
-  // (NTT_PRO_BEXT) instead of a basis_ext / modup_all launch whose output the
-  // NTT reads back (sources of at most 2 limbs, Standard ring), when the NTT
-  // runs on the two-pass kernels (fuse_bext); 0: never
-  int bext_fuse = getenv("ORION_BEXT_FUSE") ? atoi(getenv("ORION_BEXT_FUSE")) : 1;
-  // N = 2^15 inverse launches up to ntt2_tail_max limb-transforms whose last
-  // round of one-limb workgroups would be partial (jobs / (rounds * CUs) below
-  // ntt2_tail_eff) also take the two-pass kernels: a one-pass round costs one
-  // limb's latency on every CU whether or not the CU has a job, while the
-  // two-pass kernels scale with the job count (tools/ntt_bench.py, mixed
-  // moduli, inverse: 192 jobs 61 vs 76 us, 384 jobs 98 vs 127 us).  Forward
-  // launches keep the one-pass kernel: their fused epilogues cost the
-  // two-pass kernels a scratch round trip, and the LoLA bench measured them
-  // slower (profiles/r01z_ntt2_tailfwd_ab.txt)
-  double ntt2_tail_eff = getenv("ORION_NTT2_TAIL_EFF") ? atof(getenv("ORION_NTT2_TAIL_EFF")) : 0.9;
-  int ntt2_tail_max = getenv("ORION_NTT2_TAIL_MAX") ? atoi(getenv("ORION_NTT2_TAIL_MAX")) : 1024;
-  // 1: plain forward launches (load prologue, store epilogue) follow the same
-  // rule; 2: every forward launch that needs no scratch (not an in-place tail)
-  int ntt2_tail_fwd = getenv("ORION_NTT2_TAIL_FWD") ? atoi(getenv("ORION_NTT2_TAIL_FWD")) : 1;
-  int n_cu = 0;
-  int cus() {
-    if (n_cu == 0) {
-      int dev = 0;
-      HIPCHK(hipGetDevice(&dev));
-      HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    return n_cu;
-  }
-  bool ntt2_tail(int jobs) {
-    if (jobs > ntt2_tail_max || ntt2_tail_eff <= 0) return false;
-    cus();
-    const int rounds = (jobs + n_cu - 1) / n_cu;
-    return (double)jobs / ((double)rounds * n_cu) < ntt2_tail_eff;
+  // launch routes (ntt_route.h): the switches, and what init_moduli knows
+  const NttTuning tun = NttTuning::from_env();
+  NttEnv env;
+  KeySwitchRoute ks_route(int B, int level, int aut = 0, bool want_keep = false) const {
+    return keyswitch_route(env, tun, B, level, aut, want_keep);
   }
   // ORION_NTT_LOG=path: one line per NTT call ("<dispatches> <jobs> <epi> <inv>
   // <pro> <intjobs> <family>": dispatches = kernel launches of the call (1 or
@@ -1119,34 +1074,6 @@ struct Context {
     fprintf(ntt_log, "%d %d %d %d %d %d %d\n", dispatches, io.jobs, io.epi, inv ? 1 : 0,
             io.pro, io.jobs / std::max(1, io.dst.nlimb) * nint, family);
   }
-  // whether an NTT launch of `jobs` limb-transforms runs on the two-pass
-  // kernels (ntt2.hip): N = 2^16 always; N = 2^15 for small launches and for
-  // partial last rounds of inverse and plain forward launches (see above)
-  bool two_pass(int jobs, bool inv, int pro, int epi, bool inplace_sub) {
-    if (logN == 16) return true;
-    if (logN != 15 || ci) return false;
-    if (ntt_impl == 2 || jobs < ntt2_below) return true;
-    const bool plain = (pro == NTT_PRO_LOAD || pro == NTT_PRO_BEXT) && epi == NTT_EPI_STORE;
-    return (inv || (ntt2_tail_fwd == 1 && plain) || (ntt2_tail_fwd == 2 && !inplace_sub)) && ntt2_tail(jobs);
-  }
-  // the fused basis extension (NTT_PRO_BEXT) pays on the two-pass kernels
-  // only: in the one-pass kernel, one CU per limb, every target re-forms the
-  // shared y_i and float quotient and loads ns source limbs in its memory
-  // phase, and the LoLA step took 36.8 instead of 30.6 ms
-  // (profiles/r04c_bext_fuse_ab.txt); on the two-pass kernels batch 1 went
-  // from 3.0 to 2.84 ms per image
-  // and at B = 64 LoLA its partial-round two-pass launches were neutral to
-  // -0.5% (2089 / 2091 vs 2105 / 2097 img/s, profiles/r04d_bext_fuse_ab.txt),
-  // so it is kept to small launches (bext_fuse_below limb-transforms).
-  // inplace_sub: as ntt_io passes it to two_pass, so the two always agree
-  bool fuse_bext(int jobs, int ns, int epi, bool inplace_sub) {
-    return bext_fuse && ns <= 2 && !ci && jobs <= bext_fuse_below &&
-           two_pass(jobs, false, NTT_PRO_BEXT, epi, inplace_sub);
-  }
-  int bext_fuse_below = getenv("ORION_BEXT_FUSE_BELOW") ? atoi(getenv("ORION_BEXT_FUSE_BELOW")) : 64;
-  // src_per_job: NTT_PRO_BEXT launches, the mean source limbs read per
-  // limb-transform (their algorithmic bytes are (src_per_job + 1) 8 N, + 8 N
-  // for a subtract-and-scale epilogue, in the ntt_bext category)
   void prep_io(NttIO& io) {
     io.order = ntt_order;
     io.ci = ci ? 1 : 0;
@@ -1158,74 +1085,45 @@ struct Context {
           if ((host_tb.mc[io.dst.mod[l]].f64 != 0) == (pass == 1)) io.lord[k++] = (unsigned char)l;
     }
   }
-  // 1: an INTT whose output feeds only the prologue of the forward NTT that
-  // follows (ModUp and ModDown sources, the rescale's last limb) runs its rows
-  // pass alone when both launches take the latency kernels (ntt2s.hip); the
-  // forward launch finishes the INTT's columns pass on its own column tile
-  // (ntt2s_ifwd_cols), so the INTT output never goes to HBM and its second
-  // launch disappears
-  int ntt_ifuse = getenv("ORION_NTT_IFUSE") ? atoi(getenv("ORION_NTT_IFUSE")) : 1;
-  // 1: a rotation's NTT-domain automorphism is applied in the ModDown's final
-  // NTT store (NTT_EPI_SUBSCALE_AUT) where the kernel supports it
-  int ntt_aut_fuse = getenv("ORION_NTT_AUT_FUSE") ? atoi(getenv("ORION_NTT_AUT_FUSE")) : 1;
-  // ... as long as the sources' columns pass is not redone too often: every
-  // target workgroup redoes it for its own sources, (targets x sources per
-  // target) / source limbs times the INTT's own columns work (ResNet's
-  // N = 2^16 ModDowns onto 20-30 Q limbs measured slower fused)
-  double ntt_ifuse_maxr = getenv("ORION_NTT_IFUSE_MAXR") ? atof(getenv("ORION_NTT_IFUSE_MAXR")) : 8.0;
-  // 2 or 4: the fused forward runs a workgroup of that many 256-thread groups
-  // per segment of targets sharing their sources, which finishes the sources'
-  // INTT columns once for the segment (ntt2s_ifwd_cols_p); 1: one target per
-  // workgroup, the sources' columns redone for each (ntt2s_ifwd_cols)
-  int ntt_ifuse_p = getenv("ORION_NTT_IFUSE_P") ? atoi(getenv("ORION_NTT_IFUSE_P")) : 2;
-  bool on_ntt2s(int jobs, bool inv, int pro, int epi, bool inplace_sub) {
-    return (logN == 15 || logN == 16) && !ci && jobs <= ntt2s_below && two_pass(jobs, inv, pro, epi, inplace_sub);
-  }
+  // a subtract-and-scale epilogue whose operand is the destination (the
+  // routes' inplace_sub; the two-pass kernels then need a scratch intermediate)
+  static bool inplace_sub(const NttIO& io) { return io.epi != NTT_EPI_STORE && io.ex.p == io.dst.p; }
   // the INTT iio (load prologue, store epilogue) and then the forward fio whose
-  // BEXT / RESCALE prologue reads the INTT's output (fio.src = iio.dst); ns_max:
-  // the most source limbs one target reads
-  // whether intt_then_fwd(iio, fio, ns_max) takes the fused path (the INTT's
-  // rows pass alone, its columns pass inside the forward's latency kernels)
-  bool ifuse_ok(const NttIO& iio, const NttIO& fio, int ns_max) {
-    const int ij = iio.dst.ncomp * iio.dst.nlimb * iio.dst.nbatch;
-    const int fj = fio.dst.ncomp * fio.dst.nlimb * fio.dst.nbatch;
+  // BEXT / RESCALE prologue reads only the INTT's output (fio.src = iio.dst),
+  // as the route says: the two launches, or (r.ifuse) the INTT's rows pass
+  // alone, unless the producer's kernel already stored its intermediate in
+  // iio.dst (r.rows_stored), and its columns pass inside the forward's
+  // latency kernels
+  void intt_then_fwd(NttIO iio, NttIO fio, const InvFwdRoute& r, double src_per_job = 0) {
+    if (!r.ifuse) {
+      ntt_io(iio, true);
+      ntt_io(fio, false, src_per_job);
+      return;
+    }
+    // the route was computed from limb counts: the forward reads exactly what the INTT wrote
     bool same = iio.dst.p == fio.src.p && iio.dst.nlimb == fio.src.nlimb && iio.dst.ncomp == fio.src.ncomp &&
                 iio.dst.nbatch == fio.src.nbatch && iio.dst.comp_stride == fio.src.comp_stride &&
                 iio.dst.limb_stride == fio.src.limb_stride && iio.dst.batch_stride == fio.src.batch_stride;
     for (int l = 0; same && l < iio.dst.nlimb; ++l)
       same = iio.dst.pos[l] == fio.src.pos[l] && iio.dst.mod[l] == fio.src.mod[l];
-    const bool inplace_sub = fio.epi != NTT_EPI_STORE && fio.ex.p == fio.dst.p;
-    const double redo = (double)fio.dst.nlimb * ns_max / std::max(1, iio.dst.nlimb);
-    return ntt_ifuse && redo <= ntt_ifuse_maxr && same && iio.pro == NTT_PRO_LOAD && iio.epi == NTT_EPI_STORE &&
-           (fio.pro == NTT_PRO_BEXT || fio.pro == NTT_PRO_RESCALE) &&
-           on_ntt2s(ij, true, NTT_PRO_LOAD, NTT_EPI_STORE, false) && on_ntt2s(fj, false, fio.pro, fio.epi, inplace_sub);
-  }
-  // rows_done: the caller's kernel already stored the INTT's rows-pass
-  // intermediate in iio.dst (ks_mac_rows_kernel); only the fused path is valid then
-  void intt_then_fwd(NttIO iio, NttIO fio, int ns_max, double src_per_job = 0, bool rows_done = false) {
-    if (!ifuse_ok(iio, fio, ns_max)) {
-      if (rows_done) throw std::runtime_error("NTT: rows pass done, but the fused forward is not available");
-      ntt_io(iio, true);
-      ntt_io(fio, false, src_per_job);
-      return;
-    }
+    if (!same) throw std::runtime_error("NTT: the fused forward does not read the INTT's output");
     const int ij = iio.dst.ncomp * iio.dst.nlimb * iio.dst.nbatch;
     prep_io(iio);
     iio.mid = iio.dst;  // the rows pass leaves its intermediate in the INTT's own output rows
-    if (!rows_done) {
+    if (!r.rows_stored) {
       Scope sc(this, P_NTT_INV, 16.0 * N * ij);
       if (orion_launch_ntt2s(logN, iio, d_tb, true, stream, true)) throw std::runtime_error("NTT launch failed");
       log_ntt(4, iio, true);
     }
     fio.ifuse = 1;
     fio.imid = iio.dst;
-    if (NTT2S_R4 && (ntt_ifuse_p == 2 || ntt_ifuse_p == 4)) {
+    if (r.tgroup) {
       // segments: runs of target limbs on the same basis-extension table (the
       // same source limbs; the rescale prep has one source), at most G each
       int k = 0;
       for (int l = 0; l < fio.dst.nlimb;) {
         int e = l + 1;
-        while (e < fio.dst.nlimb && e - l < ntt_ifuse_p &&
+        while (e < fio.dst.nlimb && e - l < r.tgroup &&
                (fio.pro != NTT_PRO_BEXT || fio.bx_tab[e] == fio.bx_tab[l]))
           ++e;
         fio.tg_l0[k] = (unsigned char)l;
@@ -1234,10 +1132,13 @@ struct Context {
         l = e;
       }
       fio.ntg = k;
-      fio.tgroup = ntt_ifuse_p;
+      fio.tgroup = r.tgroup;
     }
     ntt_io(fio, false, src_per_job);
   }
+  // src_per_job: NTT_PRO_BEXT launches, the mean source limbs read per
+  // limb-transform (their algorithmic bytes are (src_per_job + 1) 8 N, + 8 N
+  // for a subtract-and-scale epilogue, in the ntt_bext category)
   void ntt_io(NttIO io, bool inv, double src_per_job = 0) {
     prep_io(io);
     const bool bx = io.pro == NTT_PRO_BEXT;
@@ -1250,31 +1151,32 @@ struct Context {
                        (io.epi == NTT_EPI_SUBSCALE_AUT_ACC ? 8.0 * N : 0.0);
     const double strict = 16.0 * N;
     const int cat = bx ? P_NTT_BEXT : inv ? P_NTT_INV : P_NTT_FWD;
-    if (two_pass(io.jobs, inv, io.pro, io.epi, io.epi != NTT_EPI_STORE && io.ex.p == io.dst.p)) {
+    const NttFamily fam = ntt_family(env, tun, io.jobs, inv, io.pro, io.epi, inplace_sub(io));
+    // a route's fusions name their kernels: the INTT columns pass exists in
+    // the latency kernels only, the basis-extension prologue not in ntt.hip
+    if ((io.ifuse && fam != Latency) || (bx && fam == OnePass))
+      throw std::runtime_error("NTT: the launch's fusions do not fit its kernel family");
+    if (fam != OnePass) {
       Poly scratch;
       io.mid = io.dst;
       // in-place tail: keep ex intact for pass 2; automorphism epilogue: a rows
       // workgroup stores into other rows of dst (and, accumulating, reads
       // their old words), so the intermediate cannot live there
-      if ((io.epi != NTT_EPI_STORE && io.ex.p == io.dst.p) || epi_aut(io.epi)) {
+      if (inplace_sub(io) || epi_aut(io.epi)) {
         scratch = alloc(io.dst.ncomp, io.dst.nlimb, io.dst.nbatch);
         io.mid = ls(scratch, 0, io.dst.ncomp, iota(0, io.dst.nlimb), std::vector<int>(io.dst.mod, io.dst.mod + io.dst.nlimb));
       }
       Scope sc(this, cat, per * io.jobs, strict * io.jobs);
-      const bool small = io.jobs <= ntt2s_below;
-      if (io.ifuse && !small) throw std::runtime_error("NTT: a fused INTT columns pass needs the latency kernels");
-      if (small ? orion_launch_ntt2s(logN, io, d_tb, inv, stream) : orion_launch_ntt2(logN, io, d_tb, inv, stream))
+      if (fam == Latency ? orion_launch_ntt2s(logN, io, d_tb, inv, stream) : orion_launch_ntt2(logN, io, d_tb, inv, stream))
         throw std::runtime_error("NTT launch failed");
-      log_ntt(small ? 3 : 2, io, inv);
+      log_ntt(fam, io, inv);
       return;
     }
-    if (io.ifuse) throw std::runtime_error("NTT: a fused INTT columns pass needs the latency kernels");
-    if (bx) throw std::runtime_error("NTT: a fused basis extension needs the two-pass kernels");
     // algorithmic bytes per limb-transform: read + write the limb (16 N), + 8 N
     // for the epilogue's second operand (per, above)
-    Scope sc(this, cat, per * io.dst.ncomp * io.dst.nlimb * io.dst.nbatch, strict * io.dst.ncomp * io.dst.nlimb * io.dst.nbatch);
+    Scope sc(this, cat, per * io.jobs, strict * io.jobs);
     if (orion_launch_ntt_io(logN, io, d_tb, inv, stream)) throw std::runtime_error("NTT launch failed");
-    log_ntt(1, io, inv);
+    log_ntt(fam, io, inv);
   }
   void ntt(const LimbSet& s, bool inv) { ntt_io(nio(s, s), inv); }
   void ew(int op, const LimbSet& o, const LimbSet& a, const LimbSet& b, const std::vector<u64>* sc = nullptr) {
@@ -1332,6 +1234,13 @@ struct Context {
       own_stream = true;
     }
     orion_ntt_init();
+    {
+      int dev = 0;
+      HIPCHK(hipGetDevice(&dev));
+      HIPCHK(hipDeviceGetAttribute(&env.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+      env.logN = logN, env.ci = ci, env.K = K;
+      env.max_limb = ORION_MAXLIMB, env.max_src = ORION_MAXSRC, env.max_group = ORION_MAXGROUP;
+    }
     memset(&host_tb, 0, sizeof(host_tb));
     for (int m = 0; m < L + K; ++m) build_mod_tables(m);
     HIPCHK(hipMalloc(&d_tb, sizeof(DeviceTables)));
@@ -1869,18 +1778,16 @@ struct Context {
   // positions at lvl_alloc = level.  Digit i's own Q limbs (l / K == i) equal
   // c's and are not written: every consumer (ks_mac, lt_bsgs, lt_giant) reads
   // them from c.
-  // want_cols_only: if the decomposition takes the fused latency path, its
-  // forward NTT stops after the columns pass (the caller's gadget product runs
-  // the rows pass, ks_mac_full_kernel); *cols_only tells whether it did
-  Poly decompose(const LimbSet& c, int level, int B, bool want_cols_only = false, bool* cols_only = nullptr) {
-    if (cols_only) *cols_only = false;
+  // r.cols_only: the forward NTT stops after the columns pass (the caller's
+  // gadget product runs the rows pass, ks_mac_full_kernel)
+  Poly decompose(const LimbSet& c, int level, int B, const DecomposeRoute& r) {
     const int nc = c.ncomp;
     const int beta = (level + 1 + K - 1) / K;
     const int nqp = level + 1 + K;
     Poly cinv = alloc(nc, level + 1, B);
     const NttIO iio = nio(lsq(cinv, 0, nc, level), c);  // out-of-place INTT
     Poly D = alloc(nc * beta, nqp, B);
-    if (nc * B * (nqp - K) < modup_merge && nqp <= ORION_MAXLIMB) {
+    if (r.merged) {
       // small decomposition: every digit's ModUp in one launch (own limbs not
       // written), then one NTT over every digit's target limbs: limb (digit i,
       // QP position j) of comp c sits at comp c, position i*nqp + j of a
@@ -1893,8 +1800,7 @@ struct Context {
       for (int i = 0; i < beta; ++i)
         for (int j = 0; j < nqp; ++j)
           if (!(j >= i * K && j < std::min((i + 1) * K, level + 1))) tpos.push_back(i * nqp + j), tmod.push_back(md[j]);
-      const bool tset = beta * nqp <= 256 && (int)tpos.size() <= ORION_MAXLIMB;
-      if (tset && fuse_bext(nc * B * (int)tpos.size(), K, NTT_EPI_STORE, false)) {
+      if (r.bext_pro) {
         // every digit's extension formed in the prologue of one NTT over the
         // target limbs (no modup_all launch, no round trip through HBM)
         LimbSet T = ls(D, 0, nc, tpos, tmod);
@@ -1910,11 +1816,8 @@ struct Context {
           io.bx_t[l] = (unsigned char)(j < lo ? j : j - ns);
           srcs += ns;
         }
-        if (want_cols_only && ifuse_ok(iio, io, K)) {
-          io.cols_only = 1;
-          if (cols_only) *cols_only = true;
-        }
-        intt_then_fwd(iio, io, K, srcs / (double)tpos.size());
+        io.cols_only = r.cols_only ? 1 : 0;
+        intt_then_fwd(iio, io, r.inv, srcs / (double)tpos.size());
         return D;
       }
       ntt_io(iio, true);
@@ -1923,7 +1826,7 @@ struct Context {
         if (orion_launch_modup_all(Dl, in, modup_tabs(level), beta, K, nqp, d_tb, N, stream))
           throw std::runtime_error("modup_all: bad launch shape");
       }
-      if (tset) {
+      if (r.tset) {
         LimbSet T = ls(D, 0, nc, tpos, tmod);
         T.comp_stride = (long long)beta * D.comp_stride();
         ntt(T, false);
@@ -1943,7 +1846,7 @@ struct Context {
       LimbSet in = ls(cinv, 0, nc, iota(lo, hi), iota(lo, hi));
       LimbSet out = ls(D, i, nc, tpos, tmod);
       out.comp_stride = dstride;
-      if (fuse_bext(nc * B * out.nlimb, hi - lo, NTT_EPI_STORE, false)) {  // the extension formed in the NTT's prologue
+      if (i == beta - 1 ? r.bext_pro_last : r.bext_pro) {  // the extension formed in the NTT's prologue
         NttIO io = nio(out, in);
         io.pro = NTT_PRO_BEXT;
         io.bx = T;
@@ -2008,14 +1911,6 @@ struct Context {
         throw std::runtime_error("ks_mac launch failed");
     }
   }
-  // whether the forward NTT of jobs limb-transforms with prologue pro runs on
-  // a kernel with the automorphism-scatter epilogue (NTT_EPI_SUBSCALE_AUT):
-  // the one-pass kernel with the load prologue, or the radix-4 latency kernels
-  bool aut_epi_ok(int jobs, int pro) {
-    if (ci) return false;
-    if (!two_pass(jobs, false, pro, NTT_EPI_SUBSCALE_AUT, false)) return logN <= 15 && pro == NTT_PRO_LOAD;
-    return jobs <= ntt2s_below && NTT2S_R4;  // the large two-pass kernels (ntt2.hip) have no scatter epilogue
-  }
   u64 galois_inverse(u64 g) const {
     const u64 M = nthroot;
     u64 ginv = hm_powmod(g, M / 2 - 1, M);  // g^-1 mod NthRoot (the group order divides M/2)
@@ -2030,37 +1925,18 @@ struct Context {
   // out = sigma_g of that (a rotation's NTT-domain automorphism), applied in
   // the final NTT's store when its kernel can scatter, else by automorph();
   // aut_acc: out += sigma_g(...) instead
-  // whether moddown(x, level, out, aut_g) runs its P limbs' INTT as the fused
-  // latency path, so that the gadget product before it may store those limbs
-  // after the INTT's rows pass (keyswitch, ks_mac_rows_kernel)
-  bool moddown_rows_fusable(const LimbSet& x, int level, const LimbSet& out, u64 aut_g, bool aut_acc) {
-    if (!mac_rows || (logN != 15 && logN != 16) || !NTT2S_R4) return false;
-    const int nc = x.ncomp, B = x.nbatch, jobs = nc * B * (level + 1);
-    if (!fuse_bext(jobs, K, NTT_EPI_SUBSCALE, !aut_g && out.p == x.p)) return false;
-    const bool scatter = aut_g && ntt_aut_fuse && aut_epi_ok(jobs, NTT_PRO_BEXT);
-    if (aut_g && !scatter) return false;
-    LimbSet xp = limbs(x, level + 1, K);
-    NttIO io = nio(out, xp);
-    io.pro = NTT_PRO_BEXT;
-    io.epi = !scatter ? NTT_EPI_SUBSCALE : aut_acc ? NTT_EPI_SUBSCALE_AUT_ACC : NTT_EPI_SUBSCALE_AUT;
-    io.ex = limbs(x, 0, level + 1);
-    return ifuse_ok(nio(xp, xp), io, K);
-  }
-  // 1: keyswitch's gadget product stores the P limbs through the ModDown
-  // INTT's rows pass when the ModDown takes the fused latency path
-  int mac_rows = getenv("ORION_MAC_ROWS") ? atoi(getenv("ORION_MAC_ROWS")) : 1;
-  // 1: ... and runs the decomposition NTT's forward rows pass itself
-  int mac_fwd_rows = getenv("ORION_MAC_FWD_ROWS") ? atoi(getenv("ORION_MAC_FWD_ROWS")) : 1;
   // 1: lt_bsgs / lt_giant take their workgroups in XCD-aware order (every
   // coefficient block's diagonals and keys read into one XCD's L2)
   int lt_xcd = getenv("ORION_LT_XCD") ? atoi(getenv("ORION_LT_XCD")) : 1;
-  void moddown(const LimbSet& x, int level, const LimbSet& out, u64 aut_g = 0, bool aut_acc = false,
-               bool rows_done = false) {
-    const int nc = x.ncomp, B = x.nbatch, jobs = nc * B * (level + 1);
+  // a ModDown's route where no producer stores through its rows pass
+  ModDownRoute md_route(const LimbSet& x, int level, const LimbSet& out) const {
+    return moddown_route(env, tun, x.ncomp, x.nbatch, level, 0, out.p == x.p);
+  }
+  void moddown(const LimbSet& x, int level, const LimbSet& out, const ModDownRoute& r, u64 aut_g = 0,
+               bool aut_acc = false) {
+    const int nc = x.ncomp, B = x.nbatch;
     LimbSet xp = limbs(x, level + 1, K);
-    // (with aut_g the NTT never runs in place: it scatters out of place or stores to a temporary)
-    const bool fused = fuse_bext(jobs, K, NTT_EPI_SUBSCALE, !aut_g && out.p == x.p);
-    const bool scatter = aut_g && ntt_aut_fuse && aut_epi_ok(jobs, fused ? NTT_PRO_BEXT : NTT_PRO_LOAD);
+    const bool scatter = r.scatter;
     Poly tmp;
     LimbSet dst = out;
     if (aut_g && !scatter) {  // the automorphism as its own launch, from a temporary
@@ -2068,7 +1944,7 @@ struct Context {
       dst = lsq(tmp, 0, nc, level);
     }
     auto epilogue = [&](NttIO& io) {
-      io.epi = !scatter ? NTT_EPI_SUBSCALE : aut_acc ? NTT_EPI_SUBSCALE_AUT_ACC : NTT_EPI_SUBSCALE_AUT;
+      io.epi = r.epi;
       if (scatter) {  // a scatter in place would overwrite ex words other rows still read
         if (dst.p == x.p) throw std::runtime_error("moddown: the automorphism epilogue cannot run in place");
         io.aut = aut_index(galois_inverse(aut_g));
@@ -2080,7 +1956,7 @@ struct Context {
         io.ss[j] = hm_shoup(io.s[j], mods[j]);
       }
     };
-    if (fused) {
+    if (r.bext_pro) {
       // the extension of the P limbs formed in the prologue of the NTT whose
       // epilogue is (x_Q - .) * P^-1: no basis_ext launch, no extended limbs in HBM
       NttIO io = nio(dst, xp);
@@ -2089,9 +1965,8 @@ struct Context {
       for (int j = 0; j <= level; ++j) io.bx_tab[j] = 0, io.bx_t[j] = (unsigned char)j;
       io.bx_s0[0] = 0;
       epilogue(io);
-      intt_then_fwd(nio(xp, xp), io, K, K, rows_done);
+      intt_then_fwd(nio(xp, xp), io, r.inv, K);
     } else {
-      if (rows_done) throw std::runtime_error("moddown: rows pass done, but the fused path is not taken");
       ntt(xp, true);
       Poly ext = alloc(nc, level + 1, B);
       LimbSet le = lsq(ext, 0, nc, level);
@@ -2105,12 +1980,6 @@ struct Context {
       ntt_io(io, false);
     }
     if (aut_g && !scatter) automorph(out, dst, aut_g, aut_acc);
-  }
-  // whether a ModDown at `level` that is rescaled next runs as moddown_rescale:
-  // where the ModDown takes the separate basis_ext route (small launches keep
-  // the fused latency path and the sequential rescale)
-  bool moddown_rescale_ok(int nc, int B, int level) {
-    return level >= 1 && K <= ORION_MAXSRC && !fuse_bext(nc * B * (level + 1), K, NTT_EPI_SUBSCALE, false);
   }
   // ModDown of x (as moddown's, at `level` >= 1) and the rescale of its result
   // by q_level as one division by P q_level; out: limbs 0..level-1.  Both
@@ -2148,31 +2017,22 @@ struct Context {
   // comps 0/1 of the result, folded into the gadget product as P * add; aut_g:
   // the result permuted by that Galois element's automorphism (moddown), and
   // added to out's comps 0/1 for aut_acc
-  void keyswitch(const LimbSet& c, int level, int B, const Poly& key, int klvl, const Poly& out,
-                 const u64* add0 = nullptr, const u64* add1 = nullptr, u64 aut_g = 0, bool aut_acc = false,
-                 Poly* keep_qp = nullptr) {
+  void keyswitch(const KeySwitchRoute& r, const LimbSet& c, int level, int B, const Poly& key, int klvl,
+                 Poly& out, const u64* add0 = nullptr, const u64* add1 = nullptr, u64 aut_g = 0,
+                 bool aut_acc = false) {
     if (klvl < level) throw std::runtime_error("evaluation key made for a lower level");
     Poly u = alloc(2, level + 1 + K, B);
-    if (keep_qp) {  // (the caller checked moddown_rescale_ok: no fused latency path here) no ModDown
-      Poly D = decompose(c, level, B);
-      const int beta = (level + 1 + K - 1) / K;
-      mac_groups(lsqp(u, 0, 2, level, level), 0, lsqp(D, 0, beta, level, level), 0, c, 0, {key.ptr()}, {klvl}, beta,
-                 add0, 0, add0 ? level + 1 : 0, add1, 0, false);
-      *keep_qp = u;
-      return;
-    }
-    // when the gadget product runs the ModDown INTT's rows pass, it can run
-    // the decomposition NTT's forward rows pass too (ORION_MAC_FWD_ROWS)
-    const bool rows_q = mac_fwd_rows && moddown_rows_fusable(lsqp(u, 0, 2, level, level), level,
-                                                             lsq(out, 0, 2, level), aut_g, aut_acc);
-    bool fwd_rows = false;
-    Poly D = decompose(c, level, B, rows_q, &fwd_rows);
+    Poly D = decompose(c, level, B, r.dec);
     const int beta = (level + 1 + K - 1) / K;
-    const LimbSet uq = lsqp(u, 0, 2, level, level), oq = lsq(out, 0, 2, level);
-    const bool rows = moddown_rows_fusable(uq, level, oq, aut_g, aut_acc);
+    const LimbSet uq = lsqp(u, 0, 2, level, level);
+    // the gadget product may store the P limbs through the ModDown INTT's rows
+    // pass, and then run the decomposition NTT's forward rows pass too
     mac_groups(uq, 0, lsqp(D, 0, beta, level, level), 0, c, 0, {key.ptr()}, {klvl}, beta, add0, 0,
-               add0 ? level + 1 : 0, add1, rows ? level + 1 : 0, fwd_rows);
-    moddown(uq, level, oq, aut_g, aut_acc, rows);
+               add0 ? level + 1 : 0, add1, r.mac_rows ? level + 1 : 0, r.mac_fwd_rows);
+    if (r.end == KsEnd::KeepQP)
+      out = u;  // no ModDown: the accumulator (Ciphertext::pend)
+    else
+      moddown(uq, level, lsq(out, 0, 2, level), r.md, aut_g, aut_acc);
   }
   std::vector<u64> p_mod_q(int level) const {
     std::vector<u64> v;
@@ -2207,7 +2067,8 @@ struct Context {
     if (!r.pend.buf) return;
     const int B = r.pend.B;
     Poly o = alloc(2, r.level + 1, B);
-    moddown(lsqp(r.pend, 0, 2, r.level, r.level), r.level, lsq(o, 0, 2, r.level));
+    const LimbSet x = lsqp(r.pend, 0, 2, r.level, r.level), lo = lsq(o, 0, 2, r.level);
+    moddown(x, r.level, lo, md_route(x, r.level, lo));
     r.poly = o;
     r.pend = Poly();
   }
@@ -2269,8 +2130,8 @@ struct Context {
       io.s[j] = hm_invmod(mods[l] % mods[j], mods[j]);
       io.ss[j] = hm_shoup(io.s[j], mods[j]);
     }
-    (void)B;
-    intt_then_fwd(nio(last, last), io, 1);  // INTT of the last limb, then the prep + NTT + tail
+    // INTT of the last limb, then the prep + NTT + tail
+    intt_then_fwd(nio(last, last), io, rescale_route(env, tun, 2, B, l));
     ct.level = l - 1;
     ct.scale /= (long double)mods[l];
   }
@@ -2295,15 +2156,12 @@ struct Context {
       Scope sc(this, P_TENSOR, 8.0 * N * (level + 1) * B * (square ? 5 : 7));
       orion_launch_tensor(ld, lsq(a.poly, 0, 2, level, B), lsq(b.poly, 0, 2, level, B), d_tb, N, stream);
     }
-    if (keep_qp && moddown_rescale_ok(2, B, level)) {
-      Ciphertext out = pending_ct(level, B, a.scale * b.scale);
-      keyswitch(lsq(d, 2, 1, level), level, B, rlk, L - 1, out.poly, d.ptr(), d.ptr() + d.comp_stride(), 0, false,
-                &out.pend);
-      return out;
-    }
-    Ciphertext out = new_ct(level, B, a.scale * b.scale);
+    const KeySwitchRoute r = ks_route(B, level, 0, keep_qp);
+    const bool pend = r.end == KsEnd::KeepQP;
+    Ciphertext out = pend ? pending_ct(level, B, a.scale * b.scale) : new_ct(level, B, a.scale * b.scale);
     // (d0, d1) + keyswitch(d2): the addition is folded into the gadget product
-    keyswitch(lsq(d, 2, 1, level), level, B, rlk, L - 1, out.poly, d.ptr(), d.ptr() + d.comp_stride());
+    keyswitch(r, lsq(d, 2, 1, level), level, B, rlk, L - 1, pend ? out.pend : out.poly, d.ptr(),
+              d.ptr() + d.comp_stride());
     return out;
   }
 
@@ -2315,7 +2173,8 @@ struct Context {
     const EvKey& key = galois_key(g, level);
     if (!out.poly.buf) out.poly = new_ct(level, B, a.scale).poly;
     out.level = level;
-    keyswitch(lsq(a.poly, 1, 1, level), level, B, key.k, key.level, out.poly, a.poly.ptr(), nullptr, g);
+    keyswitch(ks_route(B, level, 1), lsq(a.poly, 1, 1, level), level, B, key.k, key.level, out.poly, a.poly.ptr(),
+              nullptr, g);
   }
   // sigma_g(a): key switch of c1 with the Galois key of g, + c0, NTT-domain permutation
   // (g = 2N - 1 is the complex conjugation of the slots)
@@ -2325,7 +2184,8 @@ struct Context {
     // sigma_g((c0, 0) + keyswitch(c1)): the c0 addition folded into the gadget
     // product, the automorphism into the ModDown's store
     Ciphertext out = new_ct(level, B, a.scale);
-    keyswitch(lsq(a.poly, 1, 1, level), level, B, key.k, key.level, out.poly, a.poly.ptr(), nullptr, g);
+    keyswitch(ks_route(B, level, 1), lsq(a.poly, 1, 1, level), level, B, key.k, key.level, out.poly, a.poly.ptr(),
+              nullptr, g);
     return out;
   }
 
@@ -2337,7 +2197,8 @@ struct Context {
     const u64 g = galois_element(k);
     const int level = a.level, B = a.poly.B;
     const EvKey& key = galois_key(g, level);
-    keyswitch(lsq(a.poly, 1, 1, level), level, B, key.k, key.level, a.poly, a.poly.ptr(), nullptr, g, true);
+    keyswitch(ks_route(B, level, 2), lsq(a.poly, 1, 1, level), level, B, key.k, key.level, a.poly, a.poly.ptr(),
+              nullptr, g, true);
   }
 
   // scale matching for additions (Lattigo evaluateInPlace: the lower-scale
@@ -2471,18 +2332,19 @@ struct Context {
     const std::vector<u64> pq = p_mod_q(level);
     const int nb = (int)T.slots.size();
     const int nzb = nb - (T.slots.back() == 0 ? 1 : 0);
+    const int ng = (int)T.gorder.size();
+    const bool has_g0 = T.gorder.back() == 0;
+    const int nzg = ng - (has_g0 ? 1 : 0);
+    const LtRoute r = lt_route(env, tun, B, level, nzg, keep_qp);
 
     // 1. hoisted decomposition of ct1 (only needed when some baby rotates)
-    Poly D = nzb > 0 ? decompose(lsq(ct.poly, 1, 1, level), level, B) : alloc(1, 1, 1);
+    Poly D = nzb > 0 ? decompose(lsq(ct.poly, 1, 1, level), level, B, r.hoist) : alloc(1, 1, 1);
     LimbSet dl = lsqp(D, 0, 1, level, level);
     if (nzb == 0) dl.p = nullptr;
     LimbSet ctl = lsq(ct.poly, 0, 2, level);
 
     // 2-3. baby rotations + giant inner products (lt_bsgs): Tt comps [0, ng) =
     // c0 of giant slot gi, [ng, 2ng) = its c1
-    const int ng = (int)T.gorder.size();
-    const bool has_g0 = T.gorder.back() == 0;
-    const int nzg = ng - (has_g0 ? 1 : 0);
     Poly Tt = alloc(2 * ng, nqp, B);
     {
       const Poly& pt0 = T.diags.begin()->second.poly;
@@ -2534,20 +2396,19 @@ struct Context {
     // 4. giant key switches and the automorphism-accumulation (lt_giant)
     Poly acc = alloc(2, nqp, B);
     LimbSet la = lsqp(acc, 0, 2, level, level);
-    const bool pend = keep_qp && moddown_rescale_ok(2, B, level);
+    const bool pend = r.end == KsEnd::KeepQP;
     Ciphertext out = pend ? pending_ct(level, B, ct.scale * (long double)mods[T.level])
                           : new_ct(level, B, ct.scale * (long double)mods[T.level]);
     const LimbSet lo = pend ? la : lsq(out.poly, 0, 2, level);
     // one lt_giant launch: it may store the P limbs through the final
     // ModDown INTT's rows pass (as keyswitch's gadget product does)
-    const bool rows =
-        !pend && nzg > 0 && nzg <= ORION_MAXGROUP && moddown_rows_fusable(la, level, lo, 0, false);
+    const bool rows = r.fin.inv.rows_stored;
     LimbSet z = lsqp(Tt, ng - 1, 2, level, level);  // the zero giant: (c0, c1) at comps ng-1, 2ng-1
     z.comp_stride = (long long)ng * Tt.comp_stride();
     if (nzg > 0) {
       Poly T1q = alloc(nzg, level + 1, B);
-      moddown(lsqp(Tt, ng, nzg, level, level), level, lsq(T1q, 0, nzg, level));
-      Poly Dg = decompose(lsq(T1q, 0, nzg, level), level, B);
+      moddown(lsqp(Tt, ng, nzg, level, level), level, lsq(T1q, 0, nzg, level), r.giant_md);
+      Poly Dg = decompose(lsq(T1q, 0, nzg, level), level, B, r.giant_dec);
       for (int g0 = 0; g0 < nzg; g0 += ORION_MAXGROUP) {
         LtGiants G;
         memset(&G, 0, sizeof(G));
@@ -2595,7 +2456,7 @@ struct Context {
     if (pend)
       out.pend = acc;
     else
-      moddown(la, level, lo, 0, false, rows);
+      moddown(la, level, lo, r.fin);
     return out;
   }
 
@@ -3362,7 +3223,7 @@ struct Context {
   }
   Ciphertext lt_rescale(LinTrans& T, const Ciphertext& x) {
     // (the final ModDown and the rescale as one division where that applies)
-    Ciphertext y = eval_lt(T, x, defer_on);
+    Ciphertext y = eval_lt(T, x, true);
     if (y.pend.buf)
       finish_moddown_rescale(y);
     else
@@ -3391,7 +3252,7 @@ struct Context {
   Ciphertext run_circuit(Bootstrapper& bt, const Poly& x, int B) {
     // EvkDenseToSparse at level 0: (x0, 0) + KS(x1), now under the ephemeral secret
     Poly e = alloc(2, 1, B);
-    keyswitch(lsq(x, 1, 1, 0), 0, B, bt.d2s.k, bt.d2s.level, e, x.ptr());
+    keyswitch(ks_route(B, 0), lsq(x, 1, 1, 0), 0, B, bt.d2s.k, bt.d2s.level, e, x.ptr());
     // ModRaise: the centred level-0 residues (coefficient domain) lifted to every Q limb
     Poly c0 = alloc(2, 1, B);
     ntt_io(nio(lsq(c0, 0, 2, 0), lsq(e, 0, 2, 0)), true);
@@ -3401,7 +3262,7 @@ struct Context {
     ntt(ml, false);
     // EvkSparseToDense at the top level: (m0, 0) + KS(m1), back under the secret
     Ciphertext t = new_ct(L - 1, B, m.scale);
-    keyswitch(lsq(m.poly, 1, 1, L - 1), L - 1, B, bt.s2d.k, bt.s2d.level, t.poly, m.poly.ptr());
+    keyswitch(ks_route(B, L - 1), lsq(m.poly, 1, 1, L - 1), L - 1, B, bt.s2d.k, bt.s2d.level, t.poly, m.poly.ptr());
     const LimbSet tl = lsq(t.poly, 0, 2, L - 1);
     if (bt.gap > 1) {  // Trace: (gap^-1 t) summed over the rotations by slots * 2^i
       std::vector<u64> gi(L);
@@ -3616,7 +3477,8 @@ static void foreign_finish(Ciphertext& v, int owner) {
   const int level = v.level;
   Poly out = o->alloc(2, level + 1, v.pend.B);
   wait_on(*me, *o);
-  me->moddown(me->lsqp(v.pend, 0, 2, level, level), level, me->lsq(out, 0, 2, level));
+  const LimbSet x = me->lsqp(v.pend, 0, 2, level, level), lo = me->lsq(out, 0, 2, level);
+  me->moddown(x, level, lo, me->md_route(x, level, lo));
   wait_on(*o, *me);
   v.poly = out;
   v.pend = Poly();
@@ -4452,7 +4314,7 @@ int RotateNew(int id, int k) {
   API_BEGIN
   Context& c = ctx();
   Ciphertext& a = c.cts.get(id);
-  if (!c.defer_on) return c.cts.add(c.rotate(a, k));
+  if (!c.tun.defer) return c.cts.add(c.rotate(a, k));
   // deferred (Context::Deferred): the key is made (or checked) now, so a
   // missing key fails here as in the op-by-op path; r gets no buffer yet
   c.galois_key(c.galois_element(k), a.level);
@@ -4725,7 +4587,7 @@ int MulRelinCiphertext(int a, int b) {
 int MulRelinCiphertextNew(int a, int b) {
   API_BEGIN
   Context& c = ctx();
-  Ciphertext r = c.mul_relin(c.cts.get(a), c.cts.get(b), c.defer_on);
+  Ciphertext r = c.mul_relin(c.cts.get(a), c.cts.get(b), true);
   const bool pend = (bool)r.pend.buf;
   const int rid = c.cts.add(std::move(r));
   if (pend) c.dfr = Context::Deferred{3, -1, rid, 0};
@@ -4825,7 +4687,7 @@ int EvaluateLinearTransform(int tid, int cid) {
     std::lock_guard<std::recursive_mutex> lk(o->mu);
     if (T.plan_dirty) o->build_plan(T);
   }
-  Ciphertext r = c.eval_lt(T, c.cts.get(cid), c.defer_on);
+  Ciphertext r = c.eval_lt(T, c.cts.get(cid), true);
   const bool pend = (bool)r.pend.buf;
   const int rid = c.cts.add(std::move(r));
   if (pend) c.dfr = Context::Deferred{3, -1, rid, 0};

@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ntt_consts.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -714,19 +715,8 @@ __device__ __forceinline__ u64 bext2_apply(const Bext2& c, u64 x0, u64 x1) {
 //            NTT_EPI_SUBSCALE_AUT: the same, element e stored at position aut[e]
 //            NTT_EPI_SUBSCALE_AUT_ACC: ... added to the word at aut[e]
 // ---------------------------------------------------------------------------
-enum { NTT_PRO_LOAD = 0, NTT_PRO_RESCALE = 2, NTT_PRO_BEXT = 3 };
-// NTT_EPI_SUBSCALE_AUT: the subtract-and-scale epilogue storing element e at
-// position aut[e] -- the NTT-domain automorphism of a rotation (its scatter
-// index, the gather index of the inverse Galois element) applied in the
-// ModDown's store instead of by a separate automorph launch
-// NTT_EPI_SUBSCALE_AUT_ACC: the same, added to the word already at aut[e] (a
-// rotation whose result is added to its own input, x += sigma_g(x))
-enum { NTT_EPI_STORE = 0, NTT_EPI_SUBSCALE = 1, NTT_EPI_SUBSCALE_AUT = 2, NTT_EPI_SUBSCALE_AUT_ACC = 3 };
+// NTT_PRO_*, NTT_EPI_* and NTT2S_R4: ntt_consts.h
 __host__ __device__ constexpr bool epi_aut(int epi) { return epi == NTT_EPI_SUBSCALE_AUT || epi == NTT_EPI_SUBSCALE_AUT_ACC; }
-// 1: the latency kernels (ntt2s.hip) run in radix-4 form
-#ifndef NTT2S_R4
-#define NTT2S_R4 1
-#endif
 struct NttIO {
   LimbSet dst, src, ex;
   LimbSet mid;  // two-pass N = 2^15 kernels: intermediate between the passes (dst's geometry)

@@ -136,7 +136,7 @@ MODUP_CASES = [("small", 5, 1), ("small", 5, 48), ("k4", 7, 1), ("k4", 7, 32), (
 @pytest.mark.parametrize("name,level,B", MODUP_CASES)
 def test_modup_planted(torch_cuda, oracle_mod, name, level, B):
     """ModUp of planted digits with real keys at N = 2^13 (no NTT prologue at
-    this degree: fuse_bext needs the two-pass kernels).  decompose() takes
+    this degree: bext_in_prologue needs the two-pass kernels).  decompose() takes
     modup_all_kernel<K'> for B = 1 (nc B (level + 1) < ORION_MODUP_MERGE = 256:
     every digit in one launch) and the per-digit basis_ext_kernel<ns'> for the
     larger B; K', ns' = 2, 4 or 8 by the chain's K and the digit's limbs.
@@ -146,7 +146,7 @@ def test_modup_planted(torch_cuda, oracle_mod, name, level, B):
     (NT) and 61-bit (LAZY) ones.  k1: K = 1, every digit centred (no float
     quotient: the edges are x = s >> 1 and its neighbours, 0 and s - 1).  The
     rotation's ModDown is moddown()'s separate basis_ext_kernel; the product
-    rescaled unread runs basis_ext_rescale_kernel (moddown_rescale_ok: level >=
+    rescaled unread runs basis_ext_rescale_kernel (merged_rescale: level >=
     1 and no fused latency path)."""
     lib, orc = cached_scheme(oracle_mod, name)
     prof = check_modup(lib, orc, level, B, np.random.default_rng(100 * level + B))
@@ -247,7 +247,7 @@ def test_moddown_planted(torch_cuda, oracle_mod, name, level, B):
 
 def test_moddown_planted_ntt_prologue(torch_cuda, oracle_mod):
     """N = 2^15, B = 2, default environment: moddown() takes the fused latency
-    path (fuse_bext: 2 x 2 x 6 = 24 limb-transforms), the extension of the
+    path (bext_in_prologue: 2 x 2 x 6 = 24 limb-transforms), the extension of the
     planted P limbs formed in the prologue of the ntt2s.hip forward NTT whose
     epilogue subtracts, scales and scatters by the automorphism."""
     lib, orc = make_scheme(oracle_mod, "n15")
@@ -273,7 +273,7 @@ def test_moddown_rescale_planted(torch_cuda, oracle_mod, monkeypatch, level, B):
     linear transform with the single diagonal 1, loaded as all-ones QP rows
     (the constant 1), under unit Galois keys, so that the accumulator is the
     rotated ModUp of digit 0 of the planted c1; EvaluateLinearTransform leaves
-    its ModDown pending (moddown_rescale_ok: level >= 1, K <= 8, no fused
+    its ModDown pending (merged_rescale: level >= 1, K <= 8, no fused
     latency path at this degree) and RescaleNew runs both as one division by
     P q_level, at level 1 onto a single output limb.  Against the oracle's
     lt_bsgs -> rescale with the loaded diagonal and key, and identical with

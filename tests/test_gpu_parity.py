@@ -890,8 +890,9 @@ def test_runtime_switch_parity(torch_cuda, oracle_mod, env, B, monkeypatch):
     """The default environment and the non-default NTT / basis-extension
     paths behind the runtime switches stay bit-exact: the
     fused basis extension on large two-pass launches (ntt2.hip's
-    ntt2_fwd_cols with the NTT_PRO_BEXT prologue, where fuse_bext and ntt_io
-    must agree on the kernel family), the unfused INTT + prologue NTT, the
+    ntt2_fwd_cols with the NTT_PRO_BEXT prologue, which the route's
+    bext_in_prologue and ntt_io's ntt_family take from the same rule), the
+    unfused INTT + prologue NTT, the
     lazy-only basis extension, the INTT fusion with no redundancy limit, the
     rotation's automorphism as its own launch, and no fused basis extension
     at all (ORION_BEXT_FUSE=0: basis_ext / modup_all as their own launches,
