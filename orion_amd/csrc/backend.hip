@@ -24,6 +24,7 @@
 
 #include "../../include/orion_hip.h"
 #include "common.h"
+#include "deferral.h"
 #include "hostmath.h"
 #include "ntt_route.h"
 #include "wire.h"
@@ -399,8 +400,8 @@ struct Ciphertext {
   // buffer (Lattigo returns a copy, evaluator.go:92-99); the first in-place op
   // on either one, while both are alive, copies it first (Context::inplace_ct)
   std::shared_ptr<char> share;
-  // "ModDown pending" (Context::Deferred kind 3): the QP accumulator
-  // [Q 0..level][P] whose final ModDown has not run; poly has no buffer yet
+  // "ModDown pending" (deferral.h): the QP accumulator [Q 0..level][P] whose
+  // final ModDown has not run; poly has no buffer yet
   Poly pend;
 };
 
@@ -937,30 +938,8 @@ struct Context {
     return y;
   }
 
-  // -- deferred rotate-and-add, behind the unchanged C-ABI -------------------
-  // The frontend's `out += out.roll(k)` (linear.py:72-73 -> tensors.py:244-258,
-  // :139-167) issues RotateNew(x, k) -> r, AddCiphertext(x, r) and, when the
-  // temporary CipherTensor dies, DeleteCiphertext(r).  RotateNew only records
-  // the rotation (r gets its metadata, no buffer); the AddCiphertext that adds
-  // r into its own source records the sum; when r is then deleted unread, the
-  // pair runs as one key switch whose ModDown store adds into x
-  // (rotate_add_inplace), and r's contents are never formed.  Any other C-ABI
-  // call first runs what is pending as the op-by-op path would (defer_flush
-  // at the API layer).  ORION_DEFER=0 turns this and RescaleNew's aliasing off.
-  //
-  // "ModDown pending" (kind 3): EvaluateLinearTransform and
-  // MulRelinCiphertextNew return r with its level, scale and batch, holding
-  // the QP accumulator (Ciphertext::pend) instead of running the final
-  // ModDown, where moddown_rescale applies.  Rescale / RescaleNew of r as the
-  // next call runs both as one division by P q_l (moddown_rescale); any other
-  // call first runs the plain ModDown (metadata reads and deletes of other
-  // handles keep it pending); deleting r drops the work.  Another context
-  // that reads r runs the plain ModDown itself (foreign_finish).
-  struct Deferred {
-    int kind = 0;  // 1: r = Rotate(x, k) pending; 2: and x += r pending; 3: r's ModDown pending
-    int x = -1, r = -1, k = 0;
-  };
-  Deferred dfr;
+  // the rotation or ModDown a C-ABI call left pending (deferral.h; defer_apply)
+  deferral::Pending dfr;
 
   // lazily built tables, keys and host transfers synchronise, which would
   // invalidate an open capture (and leave HIP's stream state unusable): refuse
@@ -3463,8 +3442,8 @@ static void foreign_order(int owner, unsigned long long birth, bool always) {
   wait_on(*me, *o);
   if (!always) me->synced[owner] = stamp;
 }
-// a ciphertext of context `owner` whose ModDown is pending there (Deferred
-// kind 3), read by the acting context: the plain ModDown runs here, on this
+// a ciphertext of context `owner` whose ModDown is pending there
+// (deferral.h), read by the acting context: the plain ModDown runs here, on this
 // context's stream (which the hook has ordered after the owner's), into a
 // buffer of the owner's pool.  That buffer may have been released by work the
 // owner queued since, so this stream waits for the owner's once more; the
@@ -3610,100 +3589,69 @@ using namespace orion;
 // ---------------------------------------------------------------------------
 // C-ABI
 // ---------------------------------------------------------------------------
-// C-ABI calls that only enqueue device work (or read host metadata) may be
-// recorded into a graph; every other call is refused while a capture is open
-static bool capture_ok(const char* fn) {
-  static const std::set<std::string> ok = {
-      "Negate", "Rotate", "RotateNew", "OrionHipRotateAdd", "Rescale", "RescaleNew", "ModDropCiphertext", "AddScalar", "AddScalarNew",
-      "SubScalar", "SubScalarNew", "MulScalarInt", "MulScalarIntNew", "MulScalarFloat", "MulScalarFloatNew",
-      "AddPlaintext", "AddPlaintextNew", "SubPlaintext", "SubPlaintextNew", "MulPlaintext", "MulPlaintextNew",
-      "AddCiphertext", "AddCiphertextNew", "SubCiphertext", "SubCiphertextNew", "MulRelinCiphertext",
-      "MulRelinCiphertextNew", "EvaluateLinearTransform", "EvaluatePolynomial", "CloneCiphertext",
-      "DeleteCiphertext", "DeletePlaintext", "SetCiphertextScale", "SetPlaintextScale", "GetCiphertextScale",
-      "GetPlaintextScale", "GetCiphertextScaleF", "GetCiphertextLevel", "GetPlaintextLevel", "GetCiphertextSlots",
-      "GetPlaintextSlots", "GetCiphertextDegree", "GetCiphertextBatch", "GetPlaintextBatch", "GetLiveCiphertexts",
-      "GetLivePlaintexts", "GetModuliChain", "GaloisElement", "OrionHipGraphEnd", "OrionHipGetStream",
-      "OrionHipCurrentPipeline"};
-  return ok.count(fn) != 0;
-}
 // debugging switch ORION_DEBUG_SYNC=1: drain the library stream at the start
 // of every C-ABI call (separates an ordering race from an arithmetic fault)
 static const bool g_debug_sync = getenv("ORION_DEBUG_SYNC") && atoi(getenv("ORION_DEBUG_SYNC")) != 0;
-static void capture_guard(const char* fn) {
+// (deferral.h kCalls says which calls may be recorded into a graph)
+static void capture_guard(const deferral::Call& fn) {
   Context* c = t_act;
-  if (c && c->capturing && !capture_ok(fn))
-    throw std::runtime_error(std::string(fn) + " is not allowed while capturing a graph");
+  if (c && c->capturing && !fn.capture)
+    throw std::runtime_error(std::string(fn.name) + " is not allowed while capturing a graph");
   if (g_debug_sync && c && !c->capturing && c->stream) (void)hipStreamSynchronize(c->stream);
 }
 static int ct_ct_op(int i0, int i1, int op, bool inplace);
-// runs a deferred rotation (and the addition recorded after it) exactly as
-// the op-by-op calls would have (Context::Deferred).  If it fails, the
-// ciphertexts it should have written are poisoned: every later use of x
-// (which the AddCiphertext already reported as done) or r fails loudly with
-// this error, instead of reading a buffer that was never written
-static void poison_deferred(Context& c, const Context::Deferred& d, const char* what) {
-  const std::string msg = (d.kind == 3 ? std::string("a deferred ModDown")
-                                       : std::string("a deferred rotation by ") + std::to_string(d.k)) +
-                          " failed (" + what + "): this ciphertext was never written";
-  for (int id : {d.r, d.kind == 2 ? d.x : -1}) {
-    if (id < 0) continue;
-    try {
-      c.cts.get(id).poison = msg;
-    } catch (const std::exception&) {
-    }
-  }
-}
-static void defer_flush() {
-  if (!t_act || !t_act->dfr.kind) return;
-  Context& c = *t_act;
-  const Context::Deferred d = c.dfr;
-  c.dfr = Context::Deferred();
+// What event e makes of the context's pending work (deferral::step), carried
+// out: the one place that sets the state and runs the work.  Returns what ran.
+// If it fails, the ciphertexts it should have written are poisoned: every
+// later use of r, or of x (which the AddCiphertext already reported as done),
+// fails loudly with this error instead of reading a buffer never written.
+static deferral::Act defer_apply(Context& c, const deferral::Event& e) {
+  using namespace deferral;
+  const Pending d = c.dfr;
+  const Step s = step(d, e);
+  Act ran = s.act;
+  if (ran == Act::RecordAdd) c.inplace_ct(d.x);
+  // (another context that read r has run the ModDown: foreign_finish)
+  if (ran == Act::ModDownRescale && !c.inplace_ct(d.r).pend.buf) ran = Act::None;
+  c.dfr = s.next;
   try {
-    if (d.kind == 3) {
-      c.finish_moddown(c.cts.get(d.r));
-      return;
+    if (ran == Act::Rotate || ran == Act::RotateThenAdd) c.rotate_into(c.cts.get(d.x), d.k, c.cts.get(d.r));
+    if (ran == Act::RotateThenAdd) ct_ct_op(d.x, d.r, EW_ADD, true);
+    if (ran == Act::FusedRotateAdd) c.rotate_add_inplace(c.cts.get(d.x), d.k);
+    if (ran == Act::ModDown) c.finish_moddown(c.cts.get(d.r));
+    if (ran == Act::ModDownRescale) c.finish_moddown_rescale(c.cts.get(d.r));
+  } catch (const std::exception& err) {
+    const std::string what = d.kind == Kind::ModDown ? "ModDown" : "rotation by " + std::to_string(d.k);
+    for (int id : {d.r, d.kind == Kind::RotationAdded ? d.x : -1}) {
+      try {
+        if (id >= 0)
+          c.cts.get(id).poison =
+              "a deferred " + what + " failed (" + err.what() + "): this ciphertext was never written";
+      } catch (const std::exception&) {
+      }
     }
-    c.rotate_into(c.cts.get(d.x), d.k, c.cts.get(d.r));
-    if (d.kind == 2) ct_ct_op(d.x, d.r, EW_ADD, true);
-  } catch (const std::exception& e) {
-    poison_deferred(c, d, e.what());
     throw;
   }
+  return ran;
 }
-// C-ABI calls that leave a pending rotation pending: host metadata reads
-// (the deferred result has its level, scale and batch already), error
-// strings, and the calls that match it themselves (AddCiphertext,
-// DeleteCiphertext); every other call runs it first
-static bool defer_keeps(const char* fn) {
-  static const std::set<std::string> keep = {
-      "AddCiphertext", "DeleteCiphertext", "DeletePlaintext", "GetCiphertextScale", "GetCiphertextScaleF",
-      "GetCiphertextLevel", "GetCiphertextSlots", "GetCiphertextDegree", "GetCiphertextBatch", "GetPlaintextScale",
-      "GetPlaintextLevel", "GetPlaintextSlots", "GetPlaintextBatch", "GetLiveCiphertexts", "GetLivePlaintexts",
-      "GetModuliChain", "GaloisElement", "OrionHipPeerSelect", "OrionHipPeerCount", "OrionHipGetStream",
-      "OrionHipCurrentPipeline"};
-  return keep.count(fn) != 0;
-}
-static void defer_gate(const char* fn) {
-  if (!t_act || !t_act->dfr.kind) return;
-  // a pending ModDown is matched by Rescale / RescaleNew, which run it
-  // themselves when they name another handle (as AddCiphertext does)
-  if (t_act->dfr.kind == 3 && (!strcmp(fn, "Rescale") || !strcmp(fn, "RescaleNew"))) return;
-  if (!defer_keeps(fn)) defer_flush();
+static void api_gate(const deferral::Call& fn) {
+  capture_guard(fn);
+  if (t_act) defer_apply(*t_act, {fn.keeps ? deferral::Ev::Keeps : deferral::Ev::Flushes});
 }
 // a call acting on the calling thread's context
 #define API_BEGIN         \
   CallScope cs_;          \
   try {                   \
     cs_.act(thread_ctx(true)); \
-    capture_guard(__func__); \
-    defer_gate(__func__);
+    static const deferral::Call fn_ = deferral::call(__func__); \
+    api_gate(fn_);
 // a call acting on the context of handle `id`
 #define API_BEGIN_HANDLE(id) \
   CallScope cs_;             \
   try {                      \
     cs_.act(handle_ctx(id)); \
-    capture_guard(__func__); \
-    defer_gate(__func__);
+    static const deferral::Call fn_ = deferral::call(__func__); \
+    api_gate(fn_);
 // a call acting on no context (or on several, one at a time)
 #define API_BEGIN_NOCTX \
   CallScope cs_;        \
@@ -3939,31 +3887,11 @@ void DeletePlaintext(int id) {
 void DeleteCiphertext(int id) {
   API_BEGIN_HANDLE(id)
   Context& c = ctx();
-  const Context::Deferred d = c.dfr;
-  if (d.kind == 3) {
-    if (id == d.r) c.dfr = Context::Deferred();  // dies unread: the ModDown never runs
-  } else if (d.kind && id == d.r) {
-    c.dfr = Context::Deferred();
-    // the rotation dies unread: kind 1 needs no work at all; kind 2 is
-    // x += Rotate(x, k) with the addition in the key switch's store.  The
-    // handle goes away whatever happens; if the key switch fails, x (which
-    // the AddCiphertext reported as done) is poisoned
-    if (d.kind == 2) {
-      try {
-        c.rotate_add_inplace(c.cts.get(d.x), d.k);
-      } catch (const std::exception& e) {
-        poison_deferred(c, d, e.what());
-        c.cts.del(id);
-        throw;
-      }
-    }
-  } else if (d.kind && id == d.x) {
-    try {
-      defer_flush();
-    } catch (const std::exception&) {
-      c.cts.del(id);
-      throw;
-    }
+  try {
+    defer_apply(c, {deferral::Ev::Delete, id});
+  } catch (const std::exception&) {
+    c.cts.del(id);  // the handle goes away whatever happens
+    throw;
   }
   c.cts.del(id);
   API_END_VOID
@@ -4315,7 +4243,7 @@ int RotateNew(int id, int k) {
   Context& c = ctx();
   Ciphertext& a = c.cts.get(id);
   if (!c.tun.defer) return c.cts.add(c.rotate(a, k));
-  // deferred (Context::Deferred): the key is made (or checked) now, so a
+  // deferred (deferral.h): the key is made (or checked) now, so a
   // missing key fails here as in the op-by-op path; r gets no buffer yet
   c.galois_key(c.galois_element(k), a.level);
   Ciphertext r;
@@ -4323,7 +4251,7 @@ int RotateNew(int id, int k) {
   r.scale = a.scale;
   r.poly.B = a.poly.B;
   const int rid = c.cts.add(std::move(r));
-  c.dfr = Context::Deferred{1, id, rid, k};
+  defer_apply(c, {deferral::Ev::OpenRotation, id, rid, k});
   return rid;
   API_END(-1)
 }
@@ -4334,29 +4262,12 @@ int OrionHipRotateAdd(int id, int k) {
   return id;
   API_END(-1)
 }
-// Rescale / RescaleNew of handle id: when its ModDown is what is pending
-// (Context::Deferred kind 3), both run as one division by P q_l
+// Rescale / RescaleNew of handle id: when its ModDown is what is pending,
+// both run as one division by P q_l
 static Ciphertext& rescale_handle(Context& c, int id) {
-  const Context::Deferred d = c.dfr;
-  if (d.kind != 3 || d.r != id) {
-    defer_flush();
-    Ciphertext& a = c.inplace_ct(id);
-    c.rescale_inplace(a);
-    return a;
-  }
-  // (a refused in-place op leaves the ModDown pending: the next call runs it)
+  const bool merged = defer_apply(c, {deferral::Ev::Rescale, id}) == deferral::Act::ModDownRescale;
   Ciphertext& a = c.inplace_ct(id);
-  c.dfr = Context::Deferred();
-  if (!a.pend.buf) {  // another context read it, and ran the ModDown
-    c.rescale_inplace(a);
-    return a;
-  }
-  try {
-    c.finish_moddown_rescale(a);
-  } catch (const std::exception& e) {
-    poison_deferred(c, d, e.what());
-    throw;
-  }
+  if (!merged) c.rescale_inplace(a);
   return a;
 }
 int Rescale(int id) {
@@ -4550,12 +4461,8 @@ static int ct_ct_op(int i0, int i1, int op, bool inplace) {
 int AddCiphertext(int a, int b) {
   API_BEGIN
   Context& c = ctx();
-  if (c.dfr.kind == 1 && a == c.dfr.x && b == c.dfr.r) {  // x += (pending) Rotate(x, k): record the sum
-    c.inplace_ct(a);
-    c.dfr.kind = 2;
-    return a;
-  }
-  defer_flush();
+  // x += (pending) Rotate(x, k) is only recorded
+  if (defer_apply(c, {deferral::Ev::Add, a, b}) == deferral::Act::RecordAdd) return a;
   return ct_ct_op(a, b, EW_ADD, true);
   API_END(-1)
 }
@@ -4590,7 +4497,7 @@ int MulRelinCiphertextNew(int a, int b) {
   Ciphertext r = c.mul_relin(c.cts.get(a), c.cts.get(b), true);
   const bool pend = (bool)r.pend.buf;
   const int rid = c.cts.add(std::move(r));
-  if (pend) c.dfr = Context::Deferred{3, -1, rid, 0};
+  if (pend) defer_apply(c, {deferral::Ev::OpenModDown, rid});
   return rid;
   API_END(-1)
 }
@@ -4690,7 +4597,7 @@ int EvaluateLinearTransform(int tid, int cid) {
   Ciphertext r = c.eval_lt(T, c.cts.get(cid), true);
   const bool pend = (bool)r.pend.buf;
   const int rid = c.cts.add(std::move(r));
-  if (pend) c.dfr = Context::Deferred{3, -1, rid, 0};
+  if (pend) defer_apply(c, {deferral::Ev::OpenModDown, rid});
   return rid;
   API_END(-1)
 }

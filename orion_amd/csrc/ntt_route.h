@@ -76,7 +76,7 @@ struct NttTuning {
   // 1: ... and runs the decomposition NTT's forward rows pass itself
   int mac_fwd_rows = 1;
   // ORION_DEFER (0: off): the deferred rotate-and-add and RescaleNew's
-  // aliasing (backend.hip, Deferred), and here the ModDown left pending for a
+  // aliasing (deferral.h, backend.hip alias), and here the ModDown left pending for a
   // rescale that may follow (KsEnd::KeepQP)
   bool defer = true;
 

@@ -18,7 +18,7 @@ events that create them, so deletes and lowest-free-id reuse replay exactly.
 Every other call goes through its own C-ABI entry, in the stream's order: the
 rotate-and-add fusion of `out += out.roll(k)` (RotateNew, AddCiphertext,
 DeleteCiphertext) and RescaleNew's copy-on-write result happen inside the
-library, behind the unchanged calls (backend.hip Context::Deferred, alias).
+library, behind the unchanged calls (csrc/deferral.h, backend.hip alias).
 
 Concurrency is the frontend's own: several threads each call forward() of the
 same compiled stream on ciphertexts they encrypted themselves (Pipelines).

@@ -943,7 +943,7 @@ def test_deferred_rotate_add_plain_calls(torch_cuda, oracle_mod, B):
     """The frontend's `out += out.roll(k)` (linear.py:72-73) as the plain
     C-ABI calls it issues -- RotateNew(x, k) -> r, AddCiphertext(x, r),
     DeleteCiphertext(r) -- runs as one key switch with the addition in its
-    store (backend.hip Context::Deferred), bit-exact against orc.rotate + add,
+    store (csrc/deferral.h), bit-exact against orc.rotate + add,
     at B=64 (one-pass kernel) and B=1 (latency kernels).  Every way out of
     the deferral computes what the op-by-op calls would: the rotation read
     after the addition, the rotation read before it, the source written
