@@ -287,6 +287,53 @@ double GetCiphertextScaleF(int ct);                       /* exact-ish scale (lo
 int OrionHipStackCiphertexts(const int *cts, int n);
 int OrionHipSliceCiphertext(int ct, int first, int count);
 
+/* Blocked linear transforms: a layer whose tensors do not fit one ciphertext is
+ * an R x C matrix of BSGS transforms, out[i] = sum_j T[i][j](ct[j]).  One call
+ * evaluates the whole layer, hoisted across rows and columns: ct[j] is
+ * decomposed and its baby rotations are formed once per column, the inner sums
+ * of equal giant rotation are added across the columns before the giant step
+ * (one giant phase per row instead of C), and each row ends in one ModDown.
+ * ModDown of a sum is not the sum of ModDowns, so the result differs in its
+ * last bits from the loop of EvaluateLinearTransform / AddCiphertextNew calls;
+ * it has its own exact definition:
+ *
+ *   level = min(ct level, transform level), QP = limbs 0..level + the P limbs;
+ *   block (i,j) splits each diagonal d by its own N1 into giant(d), baby(d);
+ *   rot[j][b] = sigma_b(gadget(ct[j].c1, key_b) + (P ct[j].c0, 0))    (QP; b = 0: P ct[j])
+ *   t[i][g]   = sum_j sum_{d in T[i][j], giant(d) = g} pt[i][j][d] rot[j][baby(d)]
+ *   r[i][g]   = sigma_g(gadget(ModDown(t[i][g].c1), key_g) + (t[i][g].c0, 0)),  r[i][0] = t[i][0]
+ *   out[i]    = ModDown(sum_g r[i][g]),  scale = ct scale * q_lt;  with rescale,
+ *               Rescale of that (run as one division by P q_level where
+ *               RescaleNew after EvaluateLinearTransform does: the same bits).
+ *
+ * With C = 1 every row is bit-equal to its own EvaluateLinearTransform.
+ *
+ * OrionHipNewLinearTransformBlocks: a compiled object from rows * cols
+ * transform handles (row-major), all generated at one level, with their
+ * diagonals loaded; returns its handle.  Not allowed inside a graph capture.
+ * OrionHipEvaluateLinearTransformBlocks: cts holds cols handles of one level,
+ * bit-equal scale and batch; out receives rows new handles of the calling
+ * thread's context.  A pending deferred op runs first; a source of another
+ * context is read like any foreign operand; after one warm call it may be
+ * captured into a graph, like EvaluateLinearTransform.  Every rotation the
+ * members need must have its Galois key.
+ * OrionHipDeleteLinearTransformBlocks frees the object, not its members.
+ *
+ * The members stay ordinary transforms.  Deleting one invalidates the blocks:
+ * later evaluations fail and name it (a new transform that reuses the handle
+ * id is not mistaken for it).  Changing a member's diagonals rebuilds the
+ * merged plan at the next evaluation outside a capture.
+ *
+ * Errors: -1 and OrionHipLastError for null pointers, rows or cols < 1, an
+ * unknown handle, transforms of different levels or ciphertexts of different
+ * level, scale or batch (both handles and both values are named), a member
+ * with a diagonal that is not loaded, a missing Galois key, a column whose
+ * blocks need more than 64 distinct baby rotations, rescale at level 0, and a
+ * poisoned source.  A failed call allocates no handle. */
+int OrionHipNewLinearTransformBlocks(const int *transforms, int rows, int cols);
+int OrionHipEvaluateLinearTransformBlocks(int blocks, const int *cts, int rescale, int *out);
+void OrionHipDeleteLinearTransformBlocks(int blocks);
+
 /* GPU encoder with device-resident slots (e.g. a torch tensor's data_ptr):
  * dvalues [batch][lenPerImage] float32; DecodeDevice writes the real parts of
  * all slots, [batch][N/2] float64, to device memory (asynchronous);

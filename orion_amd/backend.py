@@ -170,6 +170,9 @@ SIGNATURES = {
     "GetCiphertextScaleF": ([c_int], c_double),
     "OrionHipStackCiphertexts": ([P(c_int), c_int], c_int),
     "OrionHipSliceCiphertext": ([c_int, c_int, c_int], c_int),
+    "OrionHipNewLinearTransformBlocks": ([P(c_int), c_int, c_int], c_int),
+    "OrionHipEvaluateLinearTransformBlocks": ([c_int, P(c_int), c_int, P(c_int)], c_int),
+    "OrionHipDeleteLinearTransformBlocks": ([c_int], None),
     "ImportCiphertext": ([P(c_ulong), c_int, c_int, c_double], c_int),
     "ExportCiphertext": ([c_int, P(c_ulong), c_ulong], c_int),
     "ImportPlaintext": ([P(c_ulong), c_int, c_int, c_double], c_int),
@@ -341,16 +344,19 @@ class HipLibrary:
         for name in SIGNATURES:
             setattr(self, name, HipFunction(self.lib, name))
         self._scheme_gen = None
+        self._blocks_shape = {}  # blocked transforms made through this object (this scheme's): handle -> (R, C)
         new, delete = self.NewScheme, self.DeleteScheme
 
         def new_scheme_call(*args):
             _SCHEME_GEN[0] += 1
             self._scheme_gen = None
+            self._blocks_shape.clear()
             new(*args)
             self._scheme_gen = _SCHEME_GEN[0]
 
         def delete_scheme_call(*args):
             _SCHEME_GEN[0] += 1
+            self._blocks_shape.clear()
             delete(*args)
 
         self.NewScheme, self.DeleteScheme = new_scheme_call, delete_scheme_call
@@ -506,6 +512,47 @@ class HipLibrary:
         """One new batch ciphertext holding images first .. first+count-1 of ct
         (OrionHipSliceCiphertext); ct stays alive."""
         return self.OrionHipSliceCiphertext(int(ct), int(first), int(count))
+
+    # ---- blocked linear transforms (include/orion_hip.h) -----------------
+    def new_linear_transform_blocks(self, ids_2d):
+        """A compiled blocked transform from an R x C nested list of transform
+        handles, all of one level (OrionHipNewLinearTransformBlocks); the
+        members stay alive and stay usable on their own."""
+        rows = [[int(t) for t in row] for row in ids_2d]
+        if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError("new_linear_transform_blocks: a non-empty rectangular list of handles is needed")
+        flat = [t for row in rows for t in row]
+        self.lib.OrionHipClearError()
+        h = self.lib.OrionHipNewLinearTransformBlocks((c_int * len(flat))(*flat), len(rows), len(rows[0]))
+        self._blocks_shape[self._chk(h, "OrionHipNewLinearTransformBlocks")] = (len(rows), len(rows[0]))
+        return h
+
+    def evaluate_linear_transform_blocks(self, blocks, cts, rescale=True, shape=None):
+        """out[i] = sum_j T[i][j](cts[j]) as one hoisted call
+        (OrionHipEvaluateLinearTransformBlocks): the C input handles (one per
+        column, of one level, scale and batch) in, the list of R new handles
+        out; rescale: each row rescaled once, as RescaleNew would.  shape:
+        (R, C), for a blocks handle that new_linear_transform_blocks of this
+        object did not make (the C call reads C handles and writes R, and takes
+        no counts)."""
+        if shape is None:
+            shape = self._blocks_shape.get(int(blocks))
+        if shape is None:
+            raise RuntimeError(f"OrionHipEvaluateLinearTransformBlocks: handle not found: {int(blocks)}")
+        cts = [int(c) for c in cts]
+        if len(cts) != shape[1]:
+            raise ValueError(f"evaluate_linear_transform_blocks: {shape[1]} input ciphertexts are needed, got {len(cts)}")
+        out = (c_int * int(shape[0]))()
+        self.lib.OrionHipClearError()
+        rc = self.lib.OrionHipEvaluateLinearTransformBlocks(int(blocks), (c_int * len(cts))(*cts),
+                                                            1 if rescale else 0, out)
+        self._chk(rc, "OrionHipEvaluateLinearTransformBlocks")
+        return [int(h) for h in out]
+
+    def delete_linear_transform_blocks(self, blocks):
+        """Free a blocked transform (its member transforms stay)."""
+        self.lib.OrionHipDeleteLinearTransformBlocks(int(blocks))
+        self._blocks_shape.pop(int(blocks), None)
 
     # Device-pointer calls run asynchronously on the library stream, which
     # torch does not know about: order them against the tensor's stream both

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "deferral.h"
 #include "hostmath.h"
+#include "lt_blocks.h"
 #include "ntt_route.h"
 #include "wire.h"
 
@@ -54,6 +55,9 @@ int orion_launch_automorph(const LimbSet& o, const LimbSet& a, const u32* idx, c
 int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
                          const LtBabies& Bb, const LtPlan* plan, int g0, int g1, int accumulate, const LimbSet& ptl,
                          const DeviceTables* tb, int N, hipStream_t st);
+int orion_launch_lt_bsgs_col(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
+                             const LtBabies& Bb, const LtColPlan* plan, int e0, int e1, int accumulate,
+                             const LimbSet& ptl, const DeviceTables* tb, int N, int colB, hipStream_t st);
 int orion_launch_lt_giant(const LimbSet& acc, const LimbSet& D, const LimbSet& own, const LimbSet& t0,
                           const LimbSet& z, const LtGiants& G, const DeviceTables* tb, int N, hipStream_t st);
 
@@ -427,6 +431,10 @@ struct LinTrans {
   std::shared_ptr<void> plan;          // owns d_plan (hipFree); captured graphs hold a reference
   int n_plan = 0;
   bool plan_dirty = true;
+  // what a blocked transform (LtBlocks) remembers of a member: uid tells this
+  // transform from a later one that reuses its handle id; rev counts the device
+  // plans built (each build makes new plan copies of the diagonals)
+  unsigned long long uid = 0, rev = 0;
   LinTrans() = default;
   LinTrans(const LinTrans&) = delete;
   LinTrans& operator=(const LinTrans&) = delete;
@@ -438,9 +446,27 @@ struct LinTrans {
     index = std::move(o.index), slots = std::move(o.slots), gorder = std::move(o.gorder);
     std::swap(d_plan, o.d_plan), std::swap(plan, o.plan), std::swap(n_plan, o.n_plan);
     plan_dirty = o.plan_dirty;
+    uid = o.uid, rev = o.rev;
     return *this;
   }
   ~LinTrans() = default;
+};
+
+// A blocked linear transform: rows x cols member transforms of one level,
+// evaluated as one call (Context::eval_lt_blocks).  The layout is lt_blocks.h's;
+// the device plans (one LtColPlan per column chunk, columns in order) point at
+// the members' plan copies of their diagonals, so they are rebuilt whenever a
+// member's plan is (LinTrans::rev).
+struct LtBlocks {
+  int rows = 0, cols = 0, level = 0;
+  std::vector<int> tids;                  // member handles, row-major
+  std::vector<unsigned long long> uids;   // ... and which transforms they named
+  std::vector<unsigned long long> revs;   // member plan revisions the device plans were built from
+  lt_blocks::Plan plan;
+  std::vector<int> first_chunk;           // per column: index of its first device plan
+  LtColPlan* d_plan = nullptr;            // = dev.get()
+  std::shared_ptr<void> dev;              // owns d_plan (hipFree); captured graphs hold a reference
+  bool built = false;
 };
 
 // a handle's context: the scheme's context is 0, pipeline i holds the ids
@@ -687,6 +713,7 @@ struct Context {
   HandlePool<Plaintext> pts;
   HandlePool<Ciphertext> cts;
   HandlePool<LinTrans> lts;
+  HandlePool<LtBlocks> ltbs;
 
   // hipGraphs captured from the library stream (OrionHipGraphBegin/End)
   struct GraphRec {
@@ -736,6 +763,7 @@ struct Context {
     pts.reset();
     cts.reset();
     lts.reset();
+    ltbs.reset();
     for (auto& kv : autidx) hipFree(kv.second);
     for (auto& kv : betab) hipFree(kv.second);
     for (auto& kv : modup_arr) hipFree(kv.second);
@@ -898,6 +926,8 @@ struct Context {
       for (auto& kv : t.sdiags) add(kv.second);
       if (t.plan) h.push_back(t.plan);
     }
+    for (int id : ltbs.live())
+      if (ltbs.get(id).dev) h.push_back(ltbs.get(id).dev);
     return h;
   }
   // in-place ops inside a capture only on ciphertexts made inside it: on an
@@ -2274,6 +2304,7 @@ struct Context {
     h2d(T.d_plan, plans.data(), nplan * sizeof(LtPlan));
     T.n_plan = nplan;
     T.plan_dirty = false;
+    ++T.rev;
   }
   // the device plans of every transform whose diagonals are all loaded (a
   // pipeline reads the scheme's transforms and never builds their plans)
@@ -2285,6 +2316,15 @@ struct Context {
       for (int d : T.idx) all = all && T.diags.count(d & (slots - 1));
       if (all) build_plan(T);
     }
+  }
+
+  // a transform can be evaluated: it has diagonals, all of them loaded
+  void lt_loaded(const LinTrans& T) const {
+    if (T.giants.empty()) throw std::runtime_error("linear transform without diagonals");
+    for (int d : T.idx)
+      if (!T.diags.count(d & (slots - 1)))
+        throw std::runtime_error("linear transform diagonal " + std::to_string(d) +
+                                 " is not loaded (io_mode load: call LoadPlaintextDiagonal first)");
   }
 
   // BSGS linear transform (lintrans MultiplyByDiagMatrixBSGS restated; oracle_lt_bsgs).
@@ -2302,11 +2342,7 @@ struct Context {
     const int level = std::min(ct.level, T.level);
     const int B = ct.poly.B, nqp = level + 1 + K;
     const int beta = (level + 1 + K - 1) / K;
-    if (T.giants.empty()) throw std::runtime_error("linear transform without diagonals");
-    for (int d : T.idx)
-      if (!T.diags.count(d & (slots - 1)))
-        throw std::runtime_error("linear transform diagonal " + std::to_string(d) +
-                                 " is not loaded (io_mode load: call LoadPlaintextDiagonal first)");
+    lt_loaded(T);
     if (T.plan_dirty) build_plan(T);
     const std::vector<u64> pq = p_mod_q(level);
     const int nb = (int)T.slots.size();
@@ -2372,12 +2408,23 @@ struct Context {
       }
     }
 
+    return lt_giant_steps(Tt, T.gorder, level, B, r, ct.scale * (long double)mods[T.level]);
+  }
+  // Steps 4 and 5 of eval_lt on the inner sums Tt of batch B: comps [0, ng) =
+  // c0 of giant slot gi, [ng, 2 ng) = its c1; gorder: the giants' amounts, the
+  // nonzero ones first, then 0 when there is one.  (A blocked transform's rows
+  // are images of Tt: eval_lt_blocks.)
+  Ciphertext lt_giant_steps(const Poly& Tt, const std::vector<int>& gorder, int level, int B, const LtRoute& r,
+                            long double scale) {
+    const int nqp = level + 1 + K, beta = (level + 1 + K - 1) / K;
+    const int ng = (int)gorder.size();
+    const bool has_g0 = gorder.back() == 0;
+    const int nzg = ng - (has_g0 ? 1 : 0);
     // 4. giant key switches and the automorphism-accumulation (lt_giant)
     Poly acc = alloc(2, nqp, B);
     LimbSet la = lsqp(acc, 0, 2, level, level);
     const bool pend = r.end == KsEnd::KeepQP;
-    Ciphertext out = pend ? pending_ct(level, B, ct.scale * (long double)mods[T.level])
-                          : new_ct(level, B, ct.scale * (long double)mods[T.level]);
+    Ciphertext out = pend ? pending_ct(level, B, scale) : new_ct(level, B, scale);
     const LimbSet lo = pend ? la : lsq(out.poly, 0, 2, level);
     // one lt_giant launch: it may store the P limbs through the final
     // ModDown INTT's rows pass (as keyswitch's gadget product does)
@@ -2404,7 +2451,7 @@ struct Context {
         G.own_gstride = T1q.comp_stride();
         G.t0_gstride = Tt.comp_stride();
         for (int k = 0; k < G.ng; ++k) {
-          const u64 g = galois_element(T.gorder[g0 + k]);
+          const u64 g = galois_element(gorder[g0 + k]);
           const EvKey& kk = galois_key(g, level);
           G.key[k] = kk.k.ptr();
           G.klvl[k] = kk.level;
@@ -2436,6 +2483,159 @@ struct Context {
       out.pend = acc;
     else
       moddown(la, level, lo, r.fin);
+    return out;
+  }
+
+  // the (giant, baby) amounts of a transform's diagonals, in the order of its index list
+  std::vector<lt_blocks::Pair> lt_pairs(const LinTrans& T) const {
+    std::vector<lt_blocks::Pair> v;
+    for (int d : T.idx) {
+      const int rot = d & (slots - 1);
+      v.push_back({((rot / T.N1) * T.N1) & (slots - 1), rot & (T.N1 - 1)});
+    }
+    return v;
+  }
+  // device plans of a blocked transform from its layout (lt_blocks.h) and the
+  // members' plan copies of their diagonals; Ts: the members, plans built
+  void build_blocks_plan(LtBlocks& Bk, const std::vector<LinTrans*>& Ts) {
+    no_capture("building a blocked linear transform's plan");
+    const lt_blocks::Plan& P = Bk.plan;
+    std::vector<LtColPlan> plans(P.total_chunks);
+    memset(plans.data(), 0, plans.size() * sizeof(LtColPlan));
+    const u64* zero = Ts[0]->sdiags.at(-1).ptr();
+    for (auto& pl : plans)
+      for (int e = 0; e < LT_MAXG; ++e)
+        for (int sl = 0; sl < LT_MAXSLOT; ++sl) pl.pt[e][sl] = zero;
+    Bk.first_chunk.clear();
+    int chunk = 0;
+    for (int j = 0; j < P.cols; ++j) {
+      const lt_blocks::Column& col = P.columns[j];
+      Bk.first_chunk.push_back(chunk);
+      for (size_t k = 0; k < col.entries.size(); ++k) {
+        const lt_blocks::Entry& en = col.entries[k];
+        LtColPlan& pl = plans[chunk + k / LT_MAXG];
+        const int e = (int)(k % LT_MAXG);
+        const LinTrans& T = *Ts[(size_t)en.row * P.cols + j];
+        pl.mask[e] = en.mask;
+        pl.comp[e] = en.gslot, pl.row[e] = en.row, pl.acc[e] = en.acc;
+        for (size_t sl = 0; sl < en.diag.size(); ++sl)
+          if (en.diag[sl] >= 0) pl.pt[e][sl] = T.sdiags.at(T.idx[en.diag[sl]] & (slots - 1)).ptr();
+      }
+      chunk += col.chunks;
+    }
+    if (!Bk.dev || Bk.dev.use_count() > 1) {  // (a plan a captured graph holds is never rewritten)
+      void* d = nullptr;
+      HIPCHK(hipMalloc(&d, plans.size() * sizeof(LtColPlan)));
+      Bk.dev = std::shared_ptr<void>(d, [](void* q) { hipFree(q); });
+      Bk.d_plan = (LtColPlan*)d;
+    }
+    h2d(Bk.d_plan, plans.data(), plans.size() * sizeof(LtColPlan));
+    Bk.revs.clear();
+    for (const LinTrans* T : Ts) Bk.revs.push_back(T->rev);
+    Bk.built = true;
+  }
+
+  // Blocked BSGS linear transform: out[i] = sum_j T[i][j](ct[j]), hoisted across
+  // rows and columns (lt_blocks.h).  Per column one decomposition and one set of
+  // baby rotations serve every row (the column form of lt_bsgs); the inner sums
+  // of equal giant amount are added across the columns in the QP basis, so each
+  // row runs one giant phase and one ModDown.  From the inner sums on the rows
+  // are images: one buffer of batch rows * B goes through eval_lt's own steps 4
+  // and 5 once.  Ts: the members (plans built); cs: the cols inputs, one level,
+  // scale and batch.  rescale: the ModDown and the rescale as one division where
+  // moddown_rescale applies, the sequence elsewhere (the same bits).
+  std::vector<Ciphertext> eval_lt_blocks(const LtBlocks& Bk, const std::vector<LinTrans*>& Ts,
+                                         const std::vector<const Ciphertext*>& cs, bool rescale) {
+    const lt_blocks::Plan& P = Bk.plan;
+    const int R = P.rows, C = P.cols;
+    const int level = std::min(cs[0]->level, Bk.level);
+    const int B = cs[0]->poly.B, RB = R * B, nqp = level + 1 + K;
+    const int beta = (level + 1 + K - 1) / K;
+    if (rescale && level < 1) throw std::runtime_error("cannot rescale a level-0 ciphertext");
+    const int ng = (int)P.giants.size();
+    const LtRoute r = lt_route(env, tun, RB, level, P.nonzero_giants, rescale);
+    const DecomposeRoute hoist = decompose_route(env, tun, 1, B, level);
+    const std::vector<u64> pq = p_mod_q(level);
+    // every key is looked up before anything is queued (galois_key throws)
+    for (int g : P.giants)
+      if (g) galois_key(galois_element(g), level);
+    for (const auto& col : P.columns)
+      for (int b : col.babies)
+        if (b) galois_key(galois_element(b), level);
+
+    // inner sums: comps [0, ng) = c0 of giant slot gs, [ng, 2 ng) = its c1; image i * B + b = row i
+    Poly Tt = alloc(2 * ng, nqp, RB);
+    const LimbSet t0 = lsqp(Tt, 0, 1, level, level), t1 = lsqp(Tt, ng, 1, level, level);
+    // (every plane of Tt is written: a row without diagonals for one of the
+    // layer's giants has an entry with an empty mask in column 0's plan)
+    const Poly& pt0 = Ts[0]->diags.begin()->second.poly;
+    const LimbSet ptl = lsqp(pt0, 0, 1, level, Bk.level, 1);
+    for (int j = 0; j < C; ++j) {
+      const lt_blocks::Column& col = P.columns[j];
+      const Ciphertext& ct = *cs[j];
+      const int nb = (int)col.babies.size();
+      // one hoisted decomposition of the column's ct1 (when some baby rotates)
+      Poly D = col.rotating > 0 ? decompose(lsq(ct.poly, 1, 1, level), level, B, hoist) : alloc(1, 1, 1);
+      LimbSet dl = lsqp(D, 0, 1, level, level);
+      if (col.rotating == 0) dl.p = nullptr;
+      const LimbSet ctl = lsq(ct.poly, 0, 2, level);
+      for (int pass = 0; pass < col.passes; ++pass) {
+        const int s0 = pass * LT_MAXB;
+        LtBabies Bb;
+        memset(&Bb, 0, sizeof(Bb));
+        Bb.nb = std::min(LT_MAXB, nb - s0);
+        Bb.s0 = s0;
+        Bb.xcd = lt_xcd && (N / 256) % 8 == 0;
+        Bb.beta = beta;
+        Bb.K = K;
+        Bb.level = level;
+        Bb.L = L;
+        for (int l = 0; l <= level; ++l) Bb.pq[l] = pq[l], Bb.pqs[l] = hm_shoup(pq[l], mods[l]);
+        int nrot = 0;
+        for (int s = 0; s < Bb.nb; ++s) {
+          const int b = col.babies[s0 + s];
+          if (b == 0) continue;
+          const u64 g = galois_element(b);
+          const EvKey& kk = galois_key(g, level);
+          Bb.key[s] = kk.k.ptr();
+          Bb.klvl[s] = kk.level;
+          Bb.idx[s] = aut_index(g);
+          ++nrot;
+        }
+        for (int k = 0; k < col.chunks; ++k) {
+          const int e0 = lt_blocks::Plan::chunk_first(k, LT_MAXG), ne = lt_blocks::Plan::chunk_count(col, k, LT_MAXG);
+          // distinct bytes, as eval_lt's: the column's decomposition and ct once
+          // per row of the launch, each entry's output pair (read back when it
+          // accumulates), the baby keys and the entries' diagonals per QP limb
+          const double lrows = (double)nqp * B;
+          int npair = 0, nacc = 0;
+          for (int e = e0; e < e0 + ne; ++e) {
+            const lt_blocks::Entry& en = col.entries[e];
+            for (int s = 0; s < Bb.nb; ++s) npair += (int)((en.mask >> (s0 + s)) & 1ull);
+            nacc += (s0 > 0 || en.acc) ? 1 : 0;
+          }
+          Scope sc(this, P_LTMAC, 8.0 * N * (lrows * ((col.rotating ? beta : 0) + 2.0 + 2.0 * (ne + nacc)) +
+                                             (double)nqp * (2.0 * beta * nrot + npair)));
+          if (orion_launch_lt_bsgs_col(t0, t1, dl, ctl, Bb, Bk.d_plan + Bk.first_chunk[j] + k, 0, ne, s0 > 0, ptl, d_tb,
+                                       N, B, stream))
+            throw std::runtime_error("lt_bsgs (column form) launch failed");
+        }
+      }
+    }
+    Ciphertext all = lt_giant_steps(Tt, P.giants, level, RB, r, cs[0]->scale * (long double)mods[Bk.level]);
+    if (all.pend.buf)
+      finish_moddown_rescale(all);
+    else if (rescale)
+      rescale_inplace(all);
+    // the rows, cut from the batch
+    std::vector<Ciphertext> out;
+    for (int i = 0; i < R; ++i) {
+      std::vector<GatherSrc> src;
+      gather_sources(all, i * B, B, src);
+      Ciphertext o = new_ct(all.level, B, all.scale);
+      gather(o, src);
+      out.push_back(std::move(o));
+    }
     return out;
   }
 
@@ -3465,12 +3665,18 @@ static void foreign_finish(Ciphertext& v, int owner) {
 static HandlePool<Ciphertext>* res_cts(int i) { Context* c = slot_ctx(i); return c ? &c->cts : nullptr; }
 static HandlePool<Plaintext>* res_pts(int i) { Context* c = slot_ctx(i); return c ? &c->pts : nullptr; }
 static HandlePool<LinTrans>* res_lts(int i) { Context* c = slot_ctx(i); return c ? &c->lts : nullptr; }
+static HandlePool<LtBlocks>* res_ltbs(int i) { Context* c = slot_ctx(i); return c ? &c->ltbs : nullptr; }
 static HandlePool<Context::PolyFn>* res_polys(int i) { Context* c = slot_ctx(i); return c ? &c->polys : nullptr; }
 static const bool g_hooks_set = [] {
   HandlePool<Ciphertext>::resolver() = res_cts;
   HandlePool<Plaintext>::resolver() = res_pts;
   HandlePool<LinTrans>::resolver() = res_lts;
   HandlePool<Context::PolyFn>::resolver() = res_polys;
+  HandlePool<LtBlocks>::resolver() = res_ltbs;
+  HandlePool<LtBlocks>::hook() = [](int o, unsigned long long b) { foreign_order(o, b, false); };
+  HandlePool<LtBlocks>::hold() = [](const LtBlocks& b) {
+    if (t_act && t_act->capturing && b.dev) t_act->capture_holds.push_back(b.dev);
+  };
   HandlePool<Ciphertext>::hook() = [](int o, unsigned long long b) { foreign_order(o, b, true); };
   HandlePool<Plaintext>::hook() = [](int o, unsigned long long b) { foreign_order(o, b, false); };
   HandlePool<LinTrans>::hook() = [](int o, unsigned long long b) { foreign_order(o, b, false); };
@@ -3523,6 +3729,7 @@ static Context* create_pipeline() {
   p->seed_encryption(g_seed + 0x9e3779b97f4a7c15ull * (u64)idx);
   const int base = idx << kCtxShift;
   p->pts.set_base(base), p->cts.set_base(base), p->lts.set_base(base), p->polys.set_base(base);
+  p->ltbs.set_base(base);
   p->next_graph = base;
   for (int j = 0; j < kMaxCtx; ++j) p->synced[j] = stamp;
   Context* r = p.get();
@@ -4541,6 +4748,7 @@ int GenerateLinearTransform(int* diagIdx, int nIdx, float* data, int nData, int 
   LinTrans T;
   T.level = level;
   T.ratio = ratio;
+  T.uid = g_birth.fetch_add(1);
   T.idx.assign(diagIdx, diagIdx + nIdx);
   const int logRatio = (int)log((double)ratio);  // lineartransform.go:67 (natural log)
   if (logRatio < 0) throw std::runtime_error("naive (non-BSGS) linear transforms are not supported");
@@ -4581,19 +4789,22 @@ int GetLinearTransformN1(int id) {
   API_END(-1)
 }
 
-int EvaluateLinearTransform(int tid, int cid) {
-  API_BEGIN
-  Context& c = ctx();
-  LinTrans& T = c.lts.get(tid);
+// another context's transform whose plan is not built (its diagonals changed
+// after the pipelines were made): its owner builds it, under its lock -- only
+// a lower-index context may be waited on (lock order)
+static void foreign_plan(Context& c, LinTrans& T, int tid) {
   Context* o = handle_ctx(tid);
   if (T.plan_dirty && o && o != &c) {
-    // another context's transform whose plan is not built (its diagonals
-    // changed after the pipelines were made): its owner builds it, under its
-    // lock -- only a lower-index context may be waited on (lock order)
     if (o->index > c.index) throw std::runtime_error("linear transform " + std::to_string(tid) + " of pipeline " + std::to_string(o->index) + " has no device plan yet: evaluate it there first");
     std::lock_guard<std::recursive_mutex> lk(o->mu);
     if (T.plan_dirty) o->build_plan(T);
   }
+}
+int EvaluateLinearTransform(int tid, int cid) {
+  API_BEGIN
+  Context& c = ctx();
+  LinTrans& T = c.lts.get(tid);
+  foreign_plan(c, T, tid);
   Ciphertext r = c.eval_lt(T, c.cts.get(cid), true);
   const bool pend = (bool)r.pend.buf;
   const int rid = c.cts.add(std::move(r));
@@ -4604,6 +4815,103 @@ int EvaluateLinearTransform(int tid, int cid) {
 void DeleteLinearTransform(int id) {
   API_BEGIN_HANDLE(id)
   ctx().lts.del(id);
+  API_END_VOID
+}
+
+// ---- blocked linear transforms (lt_blocks.h, Context::eval_lt_blocks) ----
+// the members of a blocked transform, each still the transform it was made of
+// (handle ids are reused: LinTrans::uid), its diagonals loaded and its device
+// plan built
+static std::vector<LinTrans*> blocks_members(Context& c, const LtBlocks& Bk, int bid) {
+  std::vector<LinTrans*> Ts;
+  for (size_t k = 0; k < Bk.tids.size(); ++k) {
+    const int tid = Bk.tids[k];
+    LinTrans* T = c.lts.owner_pool(tid)->has(tid) ? &c.lts.get(tid) : nullptr;
+    if (!T || T->uid != Bk.uids[k])
+      throw std::runtime_error("blocked linear transform " + std::to_string(bid) + ": its member transform " +
+                               std::to_string(tid) + " has been deleted");
+    c.lt_loaded(*T);
+    foreign_plan(c, *T, tid);
+    if (T->plan_dirty) c.build_plan(*T);
+    Ts.push_back(T);
+  }
+  return Ts;
+}
+int OrionHipNewLinearTransformBlocks(const int* tids, int rows, int cols) {
+  API_BEGIN
+  Context& c = ctx();
+  if (!tids) throw std::runtime_error("null handle list");
+  if (rows < 1 || cols < 1)
+    throw std::runtime_error("a blocked linear transform of " + std::to_string(rows) + " x " + std::to_string(cols) +
+                             " blocks: at least one row and one column are needed");
+  LtBlocks Bk;
+  Bk.rows = rows, Bk.cols = cols;
+  std::vector<std::vector<lt_blocks::Pair>> pairs;
+  for (int k = 0; k < rows * cols; ++k) {
+    const LinTrans& T = c.lts.get(tids[k]);
+    if (k == 0)
+      Bk.level = T.level;
+    else if (T.level != Bk.level)
+      throw std::runtime_error("cannot block linear transforms " + std::to_string(tids[0]) + " (level " +
+                               std::to_string(Bk.level) + ") and " + std::to_string(tids[k]) + " (level " +
+                               std::to_string(T.level) + "): the levels differ");
+    Bk.tids.push_back(tids[k]);
+    Bk.uids.push_back(T.uid);
+    pairs.push_back(c.lt_pairs(T));
+  }
+  Bk.plan = lt_blocks::plan(pairs, rows, cols, LT_MAXB, LT_MAXG, LT_MAXSLOT);
+  if (!Bk.plan.error.empty()) throw std::runtime_error(Bk.plan.error);
+  c.build_blocks_plan(Bk, blocks_members(c, Bk, -1));
+  return c.ltbs.add(std::move(Bk));
+  API_END(-1)
+}
+int OrionHipEvaluateLinearTransformBlocks(int bid, const int* cids, int rescale, int* out) {
+  API_BEGIN
+  Context& c = ctx();
+  if (!cids || !out) throw std::runtime_error("null handle list");
+  LtBlocks& Bk = c.ltbs.get(bid);
+  const std::vector<LinTrans*> Ts = blocks_members(c, Bk, bid);
+  bool dirty = !Bk.built;
+  for (size_t k = 0; k < Ts.size(); ++k) dirty = dirty || Ts[k]->rev != Bk.revs[k];
+  if (dirty) {
+    // (another context's blocks: its owner rebuilds them, as foreign_plan)
+    Context* o = handle_ctx(bid);
+    if (o && o != &c) {
+      if (o->index > c.index)
+        throw std::runtime_error("blocked linear transform " + std::to_string(bid) + " of pipeline " +
+                                 std::to_string(o->index) + " has no device plan yet: evaluate it there first");
+      std::lock_guard<std::recursive_mutex> lk(o->mu);
+      o->build_blocks_plan(Bk, Ts);
+    } else {
+      c.build_blocks_plan(Bk, Ts);
+    }
+  }
+  // every source is looked up (and checked) before anything is allocated
+  std::vector<const Ciphertext*> cs;
+  for (int j = 0; j < Bk.cols; ++j) {
+    const Ciphertext& a = c.cts.get(cids[j]);
+    const Ciphertext* f = j ? cs[0] : &a;
+    const std::string both = "blocked linear transform " + std::to_string(bid) + ": ciphertexts " +
+                             std::to_string(cids[0]) + " (";
+    if (a.level != f->level)
+      throw std::runtime_error(both + "level " + std::to_string(f->level) + ") and " + std::to_string(cids[j]) +
+                               " (level " + std::to_string(a.level) + "): the levels differ");
+    if (a.scale != f->scale)
+      throw std::runtime_error(both + "scale " + scale_str(f->scale) + ") and " + std::to_string(cids[j]) +
+                               " (scale " + scale_str(a.scale) + "): the scales differ");
+    if (a.poly.B != f->poly.B)
+      throw std::runtime_error(both + "batch " + std::to_string(f->poly.B) + ") and " + std::to_string(cids[j]) +
+                               " (batch " + std::to_string(a.poly.B) + "): the batches differ");
+    cs.push_back(&a);
+  }
+  std::vector<Ciphertext> rows = c.eval_lt_blocks(Bk, Ts, cs, rescale != 0);
+  for (int i = 0; i < Bk.rows; ++i) out[i] = c.cts.add(std::move(rows[i]));
+  return 0;
+  API_END(-1)
+}
+void OrionHipDeleteLinearTransformBlocks(int id) {
+  API_BEGIN_HANDLE(id)
+  ctx().ltbs.del(id);
   API_END_VOID
 }
 ArrayResultInt GetLinearTransformRotationKeys(int id) {

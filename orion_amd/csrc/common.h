@@ -295,6 +295,17 @@ struct LtPlan {
   unsigned long long mask[LT_MAXG];      // bit s: giant g uses baby slot s
   const u64* pt[LT_MAXG][LT_MAXSLOT];    // diagonal (QP plaintext) of (giant, slot), or null
 };
+// One chunk of a column's plan in a blocked transform (lt_blocks.h): entry e is
+// one (output row, giant) pair some block of the column has diagonals for.  Its
+// inner sum goes to component comp[e] (the giant's slot in the layer's giant
+// list) of the images row[e] * B .. row[e] * B + B - 1 of the inner-sum buffer;
+// acc[e]: an earlier column has written that plane, so this one adds to it.
+// mask and pt as LtPlan's, over the column's baby slots.
+struct LtColPlan {
+  unsigned long long mask[LT_MAXG];
+  const u64* pt[LT_MAXG][LT_MAXSLOT];
+  int comp[LT_MAXG], row[LT_MAXG], acc[LT_MAXG];
+};
 struct LtBabies {  // the baby steps of register slots [s0, s0 + nb) of one lt_bsgs launch
   const u64* key[LT_MAXB];  // Galois key of the slot (null: the zero baby)
   const u32* idx[LT_MAXB];  // its NTT-domain automorphism index

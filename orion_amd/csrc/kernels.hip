@@ -675,11 +675,30 @@ __device__ __forceinline__ void lt_xcd_decode(int& x, int& y, int& z) {
 // coefficient in registers and loops over the giants: the rotations never
 // touch HBM, and every diagonal (shared by the batch; the image index is the
 // fastest grid dimension) is read from L2.
-template <int MB>
+// PLAN = LtColPlan: the column form of a blocked transform.  The "giants" g0..g1
+// are the entries of one chunk of the column's plan, each with an output
+// component, an output row (images row * colB + bi; the grid spans colB images)
+// and its own accumulate flag -- all read from the plan at a uniform index, so
+// they stay in SGPRs.
+template <int MB, class PLAN>
 __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const LimbSet& D, const LimbSet& ct,
-                                             const LtBabies& Bb, const LtPlan* __restrict__ P, int g0, int g1,
+                                             const LtBabies& Bb, const PLAN* __restrict__ P, int g0, int g1,
                                              int accumulate, const LimbSet& ptl, const DeviceTables* __restrict__ tb,
-                                             int N, int z0) {
+                                             int N, int z0, int colB = 0) {
+  constexpr bool COL = std::is_same<PLAN, LtColPlan>::value;
+  // offset of entry g's output plane in t (t0 or t1), and whether the entry adds to it
+  auto tgo = [&](const LimbSet& t, int g) -> long long {
+    if constexpr (COL)
+      return (long long)P->comp[g] * t.comp_stride + (long long)P->row[g] * colB * t.batch_stride;
+    else
+      return (long long)(g - g0) * t.comp_stride;
+  };
+  auto adds = [&](int g) -> bool {
+    if constexpr (COL)
+      return accumulate || P->acc[g];
+    else
+      return accumulate;
+  };
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (Bb.xcd) lt_xcd_decode(bx, by, bz);
   const int bi = bx;
@@ -732,13 +751,14 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     }
     // the giant loop instantiated with and without accumulation (uniform)
     auto giants = [&](auto acc_tag) {
-      constexpr bool ACC = decltype(acc_tag)::value;
       for (int g = g0; g < g1; ++g) {
+        const bool ACC = COL ? adds(g) : decltype(acc_tag)::value;  // (the column form: per entry, uniform)
+        const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
         const unsigned long long mask = P->mask[g] >> Bb.s0;
         u64 r0 = 0, r1 = 0;
         if (ACC) {
-          r0 = t0.p[(long long)(g - g0) * t0.comp_stride + ro];
-          r1 = t1.p[(long long)(g - g0) * t1.comp_stride + ro];
+          r0 = t0.p[to0];
+          r1 = t1.p[to1];
         }
         u64 pv[MB];
 #pragma unroll
@@ -761,11 +781,11 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
         const u64 v0 = macd_reduce(a0, mc), v1 = macd_reduce(a1, mc);
         r0 = ACC ? add_mod(r0, v0, mc.q) : v0;
         r1 = ACC ? add_mod(r1, v1, mc.q) : v1;
-        t0.p[(long long)(g - g0) * t0.comp_stride + ro] = r0;
-        t1.p[(long long)(g - g0) * t1.comp_stride + ro] = r1;
+        t0.p[to0] = r0;
+        t1.p[to1] = r1;
       }
     };
-    if (accumulate) giants(std::true_type{});
+    if (!COL && accumulate) giants(std::true_type{});
     else giants(std::false_type{});
     return;
   }
@@ -782,9 +802,10 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     for (int g = g0; g < g1; ++g) {
       const unsigned long long mask = P->mask[g] >> Bb.s0;
       u64 r0 = 0, r1 = 0;
-      if (accumulate) {
-        r0 = t0.p[(long long)(g - g0) * t0.comp_stride + ro];
-        r1 = t1.p[(long long)(g - g0) * t1.comp_stride + ro];
+      const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
+      if (adds(g)) {
+        r0 = t0.p[to0];
+        r1 = t1.p[to1];
       }
       u64 pv[MB];
 #pragma unroll
@@ -809,8 +830,8 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
           macw_zero(a0), macw_zero(a1);
         }
       }
-      t0.p[(long long)(g - g0) * t0.comp_stride + ro] = r0;
-      t1.p[(long long)(g - g0) * t1.comp_stride + ro] = r1;
+      t0.p[to0] = r0;
+      t1.p[to1] = r1;
     }
     return;
   }
@@ -819,9 +840,10 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
   for (int g = g0; g < g1; ++g) {
     const unsigned long long mask = P->mask[g] >> Bb.s0;
     u64 r0 = 0, r1 = 0;
-    if (accumulate) {
-      r0 = t0.p[(long long)(g - g0) * t0.comp_stride + ro];
-      r1 = t1.p[(long long)(g - g0) * t1.comp_stride + ro];
+    const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
+    if (adds(g)) {
+      r0 = t0.p[to0];
+      r1 = t1.p[to1];
     }
     // issue every diagonal load of this giant before the first product so
     // their latencies overlap (the branches are wave-uniform)
@@ -842,8 +864,8 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
         mac_zero(a0), mac_zero(a1);
       }
     }
-    t0.p[(long long)(g - g0) * t0.comp_stride + ro] = r0;
-    t1.p[(long long)(g - g0) * t1.comp_stride + ro] = r1;
+    t0.p[to0] = r0;
+    t1.p[to1] = r1;
   }
 }
 
@@ -851,12 +873,27 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WAVES8)))
 lt_bsgs_kernel8(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int g0,
                 int g1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0) {
-  lt_bsgs_body<8>(t0, t1, D, ct, Bb, P, g0, g1, accumulate, ptl, tb, N, z0);
+  lt_bsgs_body<8, LtPlan>(t0, t1, D, ct, Bb, P, g0, g1, accumulate, ptl, tb, N, z0);
 }
 __global__ void __launch_bounds__(256)
 lt_bsgs_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int g0,
                  int g1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0) {
-  lt_bsgs_body<16>(t0, t1, D, ct, Bb, P, g0, g1, accumulate, ptl, tb, N, z0);
+  lt_bsgs_body<16, LtPlan>(t0, t1, D, ct, Bb, P, g0, g1, accumulate, ptl, tb, N, z0);
+}
+// The column form of a blocked transform: entries e0 .. e1 - 1 of one chunk of
+// the column's plan (lt_bsgs_body with PLAN = LtColPlan).  t0 / t1: components
+// 0 and ng of the layer's inner-sum buffer (batch rows * colB); the grid's
+// images are the colB images of the column's input
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WAVES8)))
+lt_bsgs_col_kernel8(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtColPlan* __restrict__ P, int e0,
+                    int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int colB) {
+  lt_bsgs_body<8, LtColPlan>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, 0, colB);
+}
+__global__ void __launch_bounds__(256)
+lt_bsgs_col_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtColPlan* __restrict__ P,
+                     int e0, int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N,
+                     int colB) {
+  lt_bsgs_body<16, LtColPlan>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, 0, colB);
 }
 
 // Giant steps of a hoisted BSGS transform, key switches and accumulation fused:
@@ -1203,6 +1240,23 @@ int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D,
   } else {
     launch(0, t0.nlimb);
   }
+  return 0;
+}
+
+// t0 / t1: batch rows * colB, every entry's row below rows; ct and D: the
+// column's colB images
+int orion_launch_lt_bsgs_col(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
+                             const LtBabies& Bb, const LtColPlan* plan, int e0, int e1, int accumulate,
+                             const LimbSet& ptl, const DeviceTables* tb, int N, int colB, hipStream_t st) {
+  if (Bb.nb < 1 || Bb.nb > LT_MAXB || e0 < 0 || e1 <= e0 || e1 > LT_MAXG) return -1;
+  if (colB < 1 || t0.nbatch % colB || ct.nbatch != colB) return -1;
+  dim3 g(colB, (N + 255) / 256, t0.nlimb);
+  if (Bb.nb <= 8)
+    hipLaunchKernelGGL(lt_bsgs_col_kernel8, g, dim3(256), 0, st, t0, t1, D, ct, Bb, plan, e0, e1, accumulate, ptl, tb,
+                       N, colB);
+  else
+    hipLaunchKernelGGL(lt_bsgs_col_kernel16, g, dim3(256), 0, st, t0, t1, D, ct, Bb, plan, e0, e1, accumulate, ptl, tb,
+                       N, colB);
   return 0;
 }
 

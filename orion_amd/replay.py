@@ -69,6 +69,119 @@ _CT_OPS = {
 _NEW_CT = ("EvaluateLinearTransform", "EvaluatePolynomial", "Bootstrap", "Negate")
 
 
+# the fork's debug decryptions inside the forward pass (not operator semantics),
+# and with the deletes of their plaintexts
+_DEBUG_DECRYPT = ("Decrypt", "Decode")
+_DEBUG_OPS = _DEBUG_DECRYPT + ("DeletePlaintext",)
+
+
+def block_groups(events):
+    """The blocked linear layers of an op stream, from its events alone.
+
+    The frontend evaluates a layer of R x C transforms as R runs of
+    EvaluateLinearTransform(T[i][j], ct[j]) summed with AddCiphertextNew and
+    rescaled once (RescaleNew), the deletes of the temporaries scattered in
+    between and after (lt_evaluator.py:155-197).  A group is a maximal sequence
+    of such rows over the same input ciphertexts, in the same order, with
+    transforms of one level, interrupted by nothing but deletes of its own
+    temporaries and the fork's debug decryptions.
+
+    Returns a list of dicts, indices counting the forward events from 0:
+    start, end (first transform, last rescale), rows, cols, lts (R x C trace
+    ids), cts (C trace ids), outs ((event index, trace id) of each row's
+    RescaleNew) and skip (every event of the group that a blocked call
+    replaces: its transforms, additions, rescales and the deletes of its
+    temporaries, those after `end` included)."""
+    level_of = {e["ret"]: e["args"][2] for e in events
+                if e["phase"] == "compile" and e["op"] == "GenerateLinearTransform"}
+    groups = []
+    cur = None        # the open group
+    row = None        # the open row: dict(start, skip, temps)
+    sym = {}          # live temporary -> its terms [(lt, ct), ...]
+    owner = {}        # live temporary -> the row or group dict whose skip list its delete joins
+
+    def close_row():  # an unfinished row: its events replay as they are
+        nonlocal row
+        if row is not None:
+            for t in row["temps"]:
+                sym.pop(t, None)
+                owner.pop(t, None)
+        row = None
+
+    def close_group():
+        nonlocal cur
+        close_row()
+        if cur is not None:
+            groups.append(cur)
+        cur = None
+
+    fi = -1
+    for e in events:
+        if e["phase"] != "forward":
+            continue
+        fi += 1
+        op, args, ret = e["op"], e["args"], e["ret"]
+        if op in _DEBUG_OPS:
+            continue
+        if op == "DeleteCiphertext":
+            x = args[0]
+            if x in owner:
+                owner.pop(x)["skip"].append(fi)
+                sym.pop(x, None)
+            elif cur is not None and x in cur["cts"]:
+                close_group()
+            elif row is not None and any(x == c for t in row["temps"] for _, c in sym.get(t, ())):
+                close_group()
+            continue
+        if op == "EvaluateLinearTransform" and args[1] not in sym:
+            if row is None:
+                row = dict(start=fi, skip=[], temps=[])
+            row["skip"].append(fi)
+            row["temps"].append(ret)
+            sym[ret], owner[ret] = [(args[0], args[1])], row
+            continue
+        if op == "AddCiphertextNew" and row is not None and args[0] in row["temps"] and args[1] in row["temps"] \
+                and args[0] in sym and args[1] in sym:
+            row["skip"].append(fi)
+            row["temps"].append(ret)
+            sym[ret], owner[ret] = sym[args[0]] + sym[args[1]], row
+            continue
+        if op == "RescaleNew" and row is not None and args[0] in row["temps"] and args[0] in sym:
+            terms = sym[args[0]]
+            lts, cts = [t for t, _ in terms], [c for _, c in terms]
+            lvl = {level_of.get(t) for t in lts}
+            if cur is not None and (cts != cur["cts"] or lvl != cur["levels"]):
+                done, row = row, None
+                close_group()
+                row = done
+            if len(lvl) != 1:  # transforms of several levels: not one blocked call
+                close_group()
+                continue
+            if cur is None:
+                cur = dict(start=row["start"], end=fi, rows=0, cols=len(cts), lts=[], cts=cts, outs=[], skip=[],
+                           levels=lvl)
+            cur["rows"] += 1
+            cur["end"] = fi
+            cur["lts"].append(lts)
+            cur["outs"].append((fi, ret))
+            cur["skip"] += row["skip"] + [fi]
+            for t in row["temps"]:  # temporaries still alive: their deletes come later
+                if owner.get(t) is row:
+                    owner[t] = cur
+            sym.pop(ret, None)
+            row = None
+            continue
+        close_group()
+        if ret is not None:
+            sym.pop(ret, None)
+            owner.pop(ret, None)
+    close_group()
+    for g in groups:
+        g.pop("levels")
+        g["skip"].sort()
+    return groups
+
+
 class OrionStream:
     """A compiled Orion model as an op stream bound to one HipLibrary."""
 
@@ -85,6 +198,8 @@ class OrionStream:
         self.pt_map, self.ct_map, self.lt_map, self.poly_map = {}, {}, {}, {}
         self.input_level = self.meta["input_level"]
         self._events = self.trace["events"]
+        self._block_acts = None  # forward(blocked=True): what replaces each grouped event
+        self.block_map = {}      # group start (forward event index) -> blocked transform handle
 
     # -- setup: keys + evaluator (key_generator.py:10-15, evaluator.py:2-6) ---
     def keygen(self, with_po2=True):
@@ -103,7 +218,8 @@ class OrionStream:
         lib.NewLinearTransformEvaluator()
 
     # -- compile phase: bias plaintexts + linear transforms + their keys --------
-    def compile(self, gen_keys=True):
+    def compile(self, gen_keys=True, blocked=False):
+        """blocked: also make the blocked transforms forward(blocked=True) calls"""
         lib = self.lib
         rng = np.random.default_rng(7)
         for ev in self._events:
@@ -135,6 +251,29 @@ class OrionStream:
             for ev in self._events:
                 if ev["phase"] == "forward" and ev["op"] in ("RotateNew", "Rotate"):
                     lib.AddRotationKey(ev["args"][1])
+        if blocked:
+            self.compile_blocks()
+
+    def compile_blocks(self):
+        """One blocked transform per layer of more than one block
+        (block_groups), made once; and, per forward event a blocked call
+        replaces, what happens instead: ("call", group) at the layer's first
+        transform, ("out", group, row) at each row's rescale, ("skip",) at the
+        rest."""
+        if self._block_acts is not None:
+            return
+        acts = {}
+        for g in block_groups(self._events):
+            if g["rows"] * g["cols"] == 1:
+                continue  # nothing to hoist: the plain calls (and their deferred ModDown) stay
+            self.block_map[g["start"]] = self.lib.new_linear_transform_blocks(
+                [[self.lt_map[t] for t in row] for row in g["lts"]])
+            for fi in g["skip"]:
+                acts[fi] = ("skip",)
+            for i, (fi, _) in enumerate(g["outs"]):
+                acts[fi] = ("out", g, i)
+            acts[g["start"]] = ("call", g)
+        self._block_acts = acts
 
     # -- bootstrapping keys for a stream without the secret key -----------------
     def bootstrap_slot_counts(self):
@@ -238,21 +377,35 @@ class OrionStream:
         return self.arrays["input"]
 
     # -- forward: the timed net(ct) ------------------------------------------------
-    def forward(self, ct_in, hook=None, stop_after=None):
+    def forward(self, ct_in, hook=None, stop_after=None, blocked=False):
         """hook(event, handle): called after every replayed op (debugging).
         stop_after: index of a forward event; the handle that event produced is
-        returned (the stream's other temporaries are deleted)."""
-        it = self.forward_iter(ct_in, hook, stop_after)
+        returned (the stream's other temporaries are deleted).  blocked: every
+        layer of R x C > 1 transforms runs as one
+        OrionHipEvaluateLinearTransformBlocks call in place of its R C
+        EvaluateLinearTransform, the additions between them and its R
+        RescaleNew (block_groups); the result differs from the plain replay's
+        in the last bits, as the blocked call's definition does.  With
+        blocked, stop_after may name a row's RescaleNew of such a layer, not
+        one of the events the call replaces (ValueError)."""
+        it = self.forward_iter(ct_in, hook, stop_after, blocked)
         while True:
             try:
                 next(it)
             except StopIteration as e:
                 return e.value
 
-    def forward_iter(self, ct_in, hook=None, stop_after=None):
+    def forward_iter(self, ct_in, hook=None, stop_after=None, blocked=False):
         """forward() one op at a time: yields after every library call that
         enqueues GPU work; the generator's return value is the output."""
         lib = self.lib
+        if blocked:
+            self.compile_blocks()
+        acts = self._block_acts if blocked else {}
+        if stop_after is not None and acts.get(stop_after, ("out",))[0] != "out":
+            raise ValueError(f"stop_after={stop_after} names an event that a blocked call replaces and that "
+                             "produces no handle: with blocked=True stop at a row's RescaleNew (block_groups: outs)")
+        rows_out = {}  # group start -> the blocked call's row handles not yet bound to a trace id
         in_ids = self.meta["input_ids"]
         ct_map = {in_ids[0]: ct_in}
         skipped_pts = set()
@@ -263,7 +416,24 @@ class OrionStream:
                 continue
             fi += 1
             op, args, ret = ev["op"], ev["args"], ev["ret"]
-            if op in ("Decrypt", "Decode"):  # debug decryptions of the fork: not operator semantics
+            act = acts.get(fi)
+            if act is not None:  # an event of a blocked layer
+                if act[0] == "call":
+                    g = act[1]
+                    hs = lib.evaluate_linear_transform_blocks(self.block_map[g["start"]],
+                                                              [ct_map[c] for c in g["cts"]], True)
+                    yield
+                    owned.update(hs)
+                    rows_out[g["start"]] = dict(enumerate(hs))
+                elif act[0] == "out":
+                    h = rows_out[act[1]["start"]].pop(act[2])
+                    if hook is not None:
+                        hook(ev, h)
+                    ct_map[ret] = h
+                    if stop_after is not None and fi == stop_after:
+                        break
+                continue
+            if op in _DEBUG_DECRYPT:  # debug decryptions of the fork: not operator semantics
                 if op == "Decrypt":
                     skipped_pts.add(ret)
                 continue
@@ -302,6 +472,9 @@ class OrionStream:
         out = ct_map[ret] if stop_after is not None else ct_map[self.meta["output_ids"][0]]
         for rid, h in ct_map.items():
             if h != out and h in owned:
+                lib.DeleteCiphertext(h)
+        for hs in rows_out.values():  # rows of a blocked call the pass stopped before binding
+            for h in hs.values():
                 lib.DeleteCiphertext(h)
         return out
 
