@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -53,11 +54,8 @@ int orion_launch_ks_mac(const LimbSet& out, const LimbSet& D, const LimbSet& own
 int orion_launch_automorph(const LimbSet& o, const LimbSet& a, const u32* idx, const DeviceTables* tb, int N,
                            int accumulate, hipStream_t st);
 int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
-                         const LtBabies& Bb, const LtPlan* plan, int g0, int g1, int accumulate, const LimbSet& ptl,
-                         const DeviceTables* tb, int N, hipStream_t st);
-int orion_launch_lt_bsgs_col(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
-                             const LtBabies& Bb, const LtColPlan* plan, int e0, int e1, int accumulate,
-                             const LimbSet& ptl, const DeviceTables* tb, int N, int colB, hipStream_t st);
+                         const LtBabies& Bb, const LtPlan* plan, int chunk, int ne, int accumulate, bool one,
+                         const LimbSet& ptl, const DeviceTables* tb, int N, int colB, hipStream_t st);
 int orion_launch_lt_giant(const LimbSet& acc, const LimbSet& D, const LimbSet& own, const LimbSet& t0,
                           const LimbSet& z, const LtGiants& G, const DeviceTables* tb, int N, hipStream_t st);
 
@@ -70,8 +68,10 @@ int orion_launch_encode_c(double2* v, int B, const double2* tw_inv, int logn, bo
                           const DeviceTables* tb, hipStream_t st);
 int orion_launch_modraise(const LimbSet& out, const LimbSet& in, const DeviceTables* tb, int N, hipStream_t st);
 
-static void bsgs_split(int rot, int slots, int N1, int* giant, int* baby);
-static int find_best_n1(const std::vector<int>& idx, int slots, int logMaxRatio);
+namespace orion {
+struct LinTrans;
+}
+static std::vector<int> lt_bsgs_index(orion::LinTrans& T, int slots, int logRatio);
 
 namespace orion {
 
@@ -416,6 +416,17 @@ struct Plaintext {
   bool qp = false;  // limbs: Q 0..level then P (LT diagonals)
 };
 
+// The layout of a blocked linear transform (lt_blocks.h) and its device plans:
+// one LtPlan per column chunk, columns in order.  They point at the members'
+// plan copies of their diagonals (Context::build_layout).  A single transform
+// holds the layout of itself as the 1 x 1 block.
+struct LtLayout {
+  lt_blocks::Plan plan;
+  std::vector<int> first_chunk;  // per column: index of its first device plan
+  LtPlan* d_plan = nullptr;      // = dev.get()
+  std::shared_ptr<void> dev;     // owns d_plan (hipFree); captured graphs hold a reference
+};
+
 struct LinTrans {
   int level = 0, N1 = 1;
   float ratio = 1;
@@ -423,13 +434,8 @@ struct LinTrans {
   std::map<int, Plaintext> diags;       // keyed by idx & (slots-1)
   std::map<int, Poly> sdiags;           // plan copies for lt_bsgs: limbs below 2^48 stored split24
   std::vector<int> giants, babies;      // sorted giants; babies in first-seen order
-  std::map<int, std::vector<int>> index;  // giant -> sorted babies
-  // device BSGS plan (built at first evaluation, rebuilt when diagonals change)
-  std::vector<int> slots;   // baby of each register slot: nonzero babies, then 0
-  std::vector<int> gorder;  // giants in evaluation order: nonzero giants, then 0
-  LtPlan* d_plan = nullptr;            // = plan.get()
-  std::shared_ptr<void> plan;          // owns d_plan (hipFree); captured graphs hold a reference
-  int n_plan = 0;
+  // the transform as a 1 x 1 block (built at first evaluation, rebuilt when diagonals change)
+  LtLayout lay;
   bool plan_dirty = true;
   // what a blocked transform (LtBlocks) remembers of a member: uid tells this
   // transform from a later one that reuses its handle id; rev counts the device
@@ -443,8 +449,7 @@ struct LinTrans {
     level = o.level, N1 = o.N1, ratio = o.ratio;
     idx = std::move(o.idx), diags = std::move(o.diags), giants = std::move(o.giants), babies = std::move(o.babies);
     sdiags = std::move(o.sdiags);
-    index = std::move(o.index), slots = std::move(o.slots), gorder = std::move(o.gorder);
-    std::swap(d_plan, o.d_plan), std::swap(plan, o.plan), std::swap(n_plan, o.n_plan);
+    std::swap(lay, o.lay);
     plan_dirty = o.plan_dirty;
     uid = o.uid, rev = o.rev;
     return *this;
@@ -453,19 +458,14 @@ struct LinTrans {
 };
 
 // A blocked linear transform: rows x cols member transforms of one level,
-// evaluated as one call (Context::eval_lt_blocks).  The layout is lt_blocks.h's;
-// the device plans (one LtColPlan per column chunk, columns in order) point at
-// the members' plan copies of their diagonals, so they are rebuilt whenever a
-// member's plan is (LinTrans::rev).
+// evaluated as one call (Context::eval_lt_blocks).  Its device plans are
+// rebuilt whenever a member's plan is (LinTrans::rev).
 struct LtBlocks {
   int rows = 0, cols = 0, level = 0;
   std::vector<int> tids;                  // member handles, row-major
   std::vector<unsigned long long> uids;   // ... and which transforms they named
   std::vector<unsigned long long> revs;   // member plan revisions the device plans were built from
-  lt_blocks::Plan plan;
-  std::vector<int> first_chunk;           // per column: index of its first device plan
-  LtColPlan* d_plan = nullptr;            // = dev.get()
-  std::shared_ptr<void> dev;              // owns d_plan (hipFree); captured graphs hold a reference
+  LtLayout lay;
   bool built = false;
 };
 
@@ -924,10 +924,10 @@ struct Context {
       LinTrans& t = lts.get(id);
       for (auto& kv : t.diags) add(kv.second.poly);
       for (auto& kv : t.sdiags) add(kv.second);
-      if (t.plan) h.push_back(t.plan);
+      if (t.lay.dev) h.push_back(t.lay.dev);
     }
     for (int id : ltbs.live())
-      if (ltbs.get(id).dev) h.push_back(ltbs.get(id).dev);
+      if (ltbs.get(id).lay.dev) h.push_back(ltbs.get(id).lay.dev);
     return h;
   }
   // in-place ops inside a capture only on ciphertexts made inside it: on an
@@ -2240,25 +2240,11 @@ struct Context {
     out.scale = a.scale;
   }
 
-  // device plan of a BSGS transform: register slot of each baby, giant order,
-  // and the diagonal plane of every (giant, slot) term
+  // device plan of a BSGS transform.  What belongs to the transform itself is
+  // made here: the plan copies of its diagonals and the zero diagonal; the plan
+  // is that of its layout as the 1 x 1 block (build_layout)
   void build_plan(LinTrans& T) {
     no_capture("building a linear transform's BSGS plan");
-    T.slots.clear();
-    T.gorder.clear();
-    bool b0 = false, g0 = false;
-    for (int b : T.babies) (b == 0 ? b0 = true : (T.slots.push_back(b), false));
-    if (b0) T.slots.push_back(0);
-    for (int j : T.giants) (j == 0 ? g0 = true : (T.gorder.push_back(j), false));
-    if (g0) T.gorder.push_back(0);
-    if ((int)T.slots.size() > LT_MAXSLOT)
-      throw std::runtime_error("linear transform with more than 64 baby steps");
-    std::map<int, int> slot_of;
-    for (size_t s = 0; s < T.slots.size(); ++s) slot_of[T.slots[s]] = (int)s;
-    const int ng = (int)T.gorder.size();
-    const int nplan = (ng + LT_MAXG - 1) / LT_MAXG;
-    std::vector<LtPlan> plans(nplan);
-    memset(plans.data(), 0, plans.size() * sizeof(LtPlan));
     // operand copies of the diagonals in lt_bsgs's split-MAC form (the
     // diagonals themselves stay canonical for serialisation)
     T.sdiags.clear();
@@ -2271,7 +2257,7 @@ struct Context {
          ls(src, 0, 1, iota(0, src.nlimb), md));
       T.sdiags.emplace(kv.first, dst);
     }
-    // a zero diagonal in every plan slot a giant does not use, so lt_bsgs can
+    // a zero diagonal in every plan slot an entry does not use, so lt_bsgs can
     // run its slots without per-slot branches (LT_DENSE; the products with it
     // add zero)
     {
@@ -2281,28 +2267,11 @@ struct Context {
       HIPCHK(hipMemsetAsync(z.ptr(), 0, (size_t)any.ncomp * any.nlimb * any.B * N * sizeof(u64), stream));
       T.sdiags.emplace(-1, z);
     }
-    for (auto& P : plans)
-      for (int gg = 0; gg < LT_MAXG; ++gg)
-        for (int sl = 0; sl < LT_MAXSLOT; ++sl) P.pt[gg][sl] = T.sdiags.at(-1).ptr();
-    for (int gi = 0; gi < ng; ++gi) {
-      LtPlan& P = plans[gi / LT_MAXG];
-      const int j = T.gorder[gi], gg = gi % LT_MAXG;
-      for (int b : T.index.at(j)) {
-        const int sl = slot_of.at(b);
-        P.mask[gg] |= 1ull << sl;
-        P.pt[gg][sl] = T.sdiags.at((j + b) & (slots - 1)).ptr();
-      }
-    }
-    // a plan that a captured graph still holds is never rewritten: the graph
-    // keeps replaying the plan (and the diagonals) it was captured with
-    if (!T.plan || T.n_plan != nplan || T.plan.use_count() > 1) {
-      void* d = nullptr;
-      HIPCHK(hipMalloc(&d, nplan * sizeof(LtPlan)));
-      T.plan = std::shared_ptr<void>(d, [](void* q) { hipFree(q); });
-      T.d_plan = (LtPlan*)d;
-    }
-    h2d(T.d_plan, plans.data(), nplan * sizeof(LtPlan));
-    T.n_plan = nplan;
+    T.lay.plan = lt_blocks::plan({lt_pairs(T)}, 1, 1, LT_MAXB, LT_MAXG, LT_MAXSLOT);
+    if (!T.lay.plan.error.empty())  // (worded for one transform)
+      throw std::runtime_error(T.idx.empty() ? "linear transform without diagonals"
+                                             : "linear transform with more than 64 baby steps");
+    build_layout(T.lay, {&T});
     T.plan_dirty = false;
     ++T.rev;
   }
@@ -2327,93 +2296,19 @@ struct Context {
                                  " is not loaded (io_mode load: call LoadPlaintextDiagonal first)");
   }
 
-  // BSGS linear transform (lintrans MultiplyByDiagMatrixBSGS restated; oracle_lt_bsgs).
-  // Every phase runs as one grouped launch over all babies / all giants:
-  //   1. one hoisted decomposition of ct1;
-  //   2. all baby key switches (one MAC, decomposition shared) and their
-  //      automorphisms with the + P*ct0 term (one launch);
-  //   3. all giant inner products sum_s pt * rot_s (lt_bsgs: each baby read once);
-  //   4. all giant key switches: ModDown of c1, decomposition, MAC with each
-  //      giant's key (+ c0 folded in), then the automorphism-accumulate;
-  //   5. ModDown of the accumulator.
-  // keep_qp: where moddown_rescale would apply, step 5 is left out and the
-  // result holds the accumulator instead (Ciphertext::pend)
+  // BSGS linear transform (lintrans MultiplyByDiagMatrixBSGS restated; oracle_lt_bsgs):
+  // the transform's own layout, the 1 x 1 block, through eval_layout.
+  // keep_qp: where moddown_rescale would apply, the final ModDown is left out
+  // and the result holds the accumulator instead (Ciphertext::pend)
   Ciphertext eval_lt(LinTrans& T, const Ciphertext& ct, bool keep_qp = false) {
-    const int level = std::min(ct.level, T.level);
-    const int B = ct.poly.B, nqp = level + 1 + K;
-    const int beta = (level + 1 + K - 1) / K;
     lt_loaded(T);
     if (T.plan_dirty) build_plan(T);
-    const std::vector<u64> pq = p_mod_q(level);
-    const int nb = (int)T.slots.size();
-    const int nzb = nb - (T.slots.back() == 0 ? 1 : 0);
-    const int ng = (int)T.gorder.size();
-    const bool has_g0 = T.gorder.back() == 0;
-    const int nzg = ng - (has_g0 ? 1 : 0);
-    const LtRoute r = lt_route(env, tun, B, level, nzg, keep_qp);
-
-    // 1. hoisted decomposition of ct1 (only needed when some baby rotates)
-    Poly D = nzb > 0 ? decompose(lsq(ct.poly, 1, 1, level), level, B, r.hoist) : alloc(1, 1, 1);
-    LimbSet dl = lsqp(D, 0, 1, level, level);
-    if (nzb == 0) dl.p = nullptr;
-    LimbSet ctl = lsq(ct.poly, 0, 2, level);
-
-    // 2-3. baby rotations + giant inner products (lt_bsgs): Tt comps [0, ng) =
-    // c0 of giant slot gi, [ng, 2ng) = its c1
-    Poly Tt = alloc(2 * ng, nqp, B);
-    {
-      const Poly& pt0 = T.diags.begin()->second.poly;
-      LimbSet ptl = lsqp(pt0, 0, 1, level, T.level, 1);
-      for (int s0 = 0; s0 < nb; s0 += LT_MAXB) {
-        LtBabies Bb;
-        memset(&Bb, 0, sizeof(Bb));
-        Bb.nb = std::min(LT_MAXB, nb - s0);
-        Bb.s0 = s0;
-        Bb.xcd = lt_xcd && (N / 256) % 8 == 0;
-        Bb.beta = beta;
-        Bb.K = K;
-        Bb.level = level;
-        Bb.L = L;
-        for (int j = 0; j <= level; ++j) Bb.pq[j] = pq[j], Bb.pqs[j] = hm_shoup(pq[j], mods[j]);
-        int nrot = 0;
-        for (int s = 0; s < Bb.nb; ++s) {
-          const int b = T.slots[s0 + s];
-          if (b == 0) continue;
-          const u64 g = galois_element(b);
-          const EvKey& kk = galois_key(g, level);
-          Bb.key[s] = kk.k.ptr();
-          Bb.klvl[s] = kk.level;
-          Bb.idx[s] = aut_index(g);
-          ++nrot;
-        }
-        for (int p = 0; p < T.n_plan; ++p) {
-          const int gcount = std::min(LT_MAXG, ng - p * LT_MAXG);
-          LimbSet t0 = lsqp(Tt, p * LT_MAXG, 1, level, level), t1 = lsqp(Tt, ng + p * LT_MAXG, 1, level, level);
-          // distinct bytes: the shared decomposition (beta digits) and ct0/ct1
-          // once per row, the giant outputs (read back when accumulating), and
-          // per QP limb the baby keys (2 beta each) and the diagonals of the
-          // plan's (giant, baby) terms, both shared by the batch
-          const double rows = (double)nqp * B;
-          int npair = 0;
-          for (int gi = p * LT_MAXG; gi < p * LT_MAXG + gcount; ++gi)
-            for (int b : T.index.at(T.gorder[gi]))
-              for (int s = 0; s < Bb.nb; ++s)
-                if (T.slots[s0 + s] == b) ++npair;
-          Scope sc(this, P_LTMAC,
-                   8.0 * N * (rows * ((nzb ? beta : 0) + 2.0 + 2.0 * gcount * (s0 ? 2 : 1)) +
-                              (double)nqp * (2.0 * beta * nrot + npair)));
-          if (orion_launch_lt_bsgs(t0, t1, dl, ctl, Bb, T.d_plan + p, 0, gcount, s0 > 0, ptl, d_tb, N, stream))
-            throw std::runtime_error("lt_bsgs launch failed");
-        }
-      }
-    }
-
-    return lt_giant_steps(Tt, T.gorder, level, B, r, ct.scale * (long double)mods[T.level]);
+    return eval_layout(T.lay, T, {&ct}, keep_qp);
   }
-  // Steps 4 and 5 of eval_lt on the inner sums Tt of batch B: comps [0, ng) =
+  // Steps 4 and 5 of eval_layout on the inner sums Tt of batch B: comps [0, ng) =
   // c0 of giant slot gi, [ng, 2 ng) = its c1; gorder: the giants' amounts, the
   // nonzero ones first, then 0 when there is one.  (A blocked transform's rows
-  // are images of Tt: eval_lt_blocks.)
+  // are images of Tt.)
   Ciphertext lt_giant_steps(const Poly& Tt, const std::vector<int>& gorder, int level, int B, const LtRoute& r,
                             long double scale) {
     const int nqp = level + 1 + K, beta = (level + 1 + K - 1) / K;
@@ -2495,25 +2390,24 @@ struct Context {
     }
     return v;
   }
-  // device plans of a blocked transform from its layout (lt_blocks.h) and the
-  // members' plan copies of their diagonals; Ts: the members, plans built
-  void build_blocks_plan(LtBlocks& Bk, const std::vector<LinTrans*>& Ts) {
-    no_capture("building a blocked linear transform's plan");
-    const lt_blocks::Plan& P = Bk.plan;
-    std::vector<LtColPlan> plans(P.total_chunks);
-    memset(plans.data(), 0, plans.size() * sizeof(LtColPlan));
+  // device plans of a layout (lt_blocks.h) from the members' plan copies of
+  // their diagonals; Ts: the members, row-major, their copies made
+  void build_layout(LtLayout& Ly, const std::vector<LinTrans*>& Ts) {
+    const lt_blocks::Plan& P = Ly.plan;
+    std::vector<LtPlan> plans(P.total_chunks);
+    memset(plans.data(), 0, plans.size() * sizeof(LtPlan));
     const u64* zero = Ts[0]->sdiags.at(-1).ptr();
     for (auto& pl : plans)
       for (int e = 0; e < LT_MAXG; ++e)
         for (int sl = 0; sl < LT_MAXSLOT; ++sl) pl.pt[e][sl] = zero;
-    Bk.first_chunk.clear();
+    Ly.first_chunk.clear();
     int chunk = 0;
     for (int j = 0; j < P.cols; ++j) {
       const lt_blocks::Column& col = P.columns[j];
-      Bk.first_chunk.push_back(chunk);
+      Ly.first_chunk.push_back(chunk);
       for (size_t k = 0; k < col.entries.size(); ++k) {
         const lt_blocks::Entry& en = col.entries[k];
-        LtColPlan& pl = plans[chunk + k / LT_MAXG];
+        LtPlan& pl = plans[chunk + k / LT_MAXG];
         const int e = (int)(k % LT_MAXG);
         const LinTrans& T = *Ts[(size_t)en.row * P.cols + j];
         pl.mask[e] = en.mask;
@@ -2523,37 +2417,49 @@ struct Context {
       }
       chunk += col.chunks;
     }
-    if (!Bk.dev || Bk.dev.use_count() > 1) {  // (a plan a captured graph holds is never rewritten)
+    // a plan that a captured graph still holds is never rewritten: the graph
+    // keeps replaying the plan (and the diagonals) it was captured with
+    if (!Ly.dev || Ly.dev.use_count() > 1) {
       void* d = nullptr;
-      HIPCHK(hipMalloc(&d, plans.size() * sizeof(LtColPlan)));
-      Bk.dev = std::shared_ptr<void>(d, [](void* q) { hipFree(q); });
-      Bk.d_plan = (LtColPlan*)d;
+      HIPCHK(hipMalloc(&d, plans.size() * sizeof(LtPlan)));
+      Ly.dev = std::shared_ptr<void>(d, [](void* q) { hipFree(q); });
+      Ly.d_plan = (LtPlan*)d;
     }
-    h2d(Bk.d_plan, plans.data(), plans.size() * sizeof(LtColPlan));
+    h2d(Ly.d_plan, plans.data(), plans.size() * sizeof(LtPlan));
+  }
+  // ... of a blocked transform; Ts: the members, plans built
+  void build_blocks_plan(LtBlocks& Bk, const std::vector<LinTrans*>& Ts) {
+    no_capture("building a blocked linear transform's plan");
+    build_layout(Bk.lay, Ts);
     Bk.revs.clear();
     for (const LinTrans* T : Ts) Bk.revs.push_back(T->rev);
     Bk.built = true;
   }
 
-  // Blocked BSGS linear transform: out[i] = sum_j T[i][j](ct[j]), hoisted across
-  // rows and columns (lt_blocks.h).  Per column one decomposition and one set of
-  // baby rotations serve every row (the column form of lt_bsgs); the inner sums
-  // of equal giant amount are added across the columns in the QP basis, so each
-  // row runs one giant phase and one ModDown.  From the inner sums on the rows
-  // are images: one buffer of batch rows * B goes through eval_lt's own steps 4
-  // and 5 once.  Ts: the members (plans built); cs: the cols inputs, one level,
-  // scale and batch.  rescale: the ModDown and the rescale as one division where
-  // moddown_rescale applies, the sequence elsewhere (the same bits).
-  std::vector<Ciphertext> eval_lt_blocks(const LtBlocks& Bk, const std::vector<LinTrans*>& Ts,
-                                         const std::vector<const Ciphertext*>& cs, bool rescale) {
-    const lt_blocks::Plan& P = Bk.plan;
-    const int R = P.rows, C = P.cols;
-    const int level = std::min(cs[0]->level, Bk.level);
-    const int B = cs[0]->poly.B, RB = R * B, nqp = level + 1 + K;
+  // BSGS linear transform of a layout (lt_blocks.h): all rows' sum_j T[i][j](ct[j])
+  // as one batch, image i * B + b = row i.  Every phase runs as one grouped
+  // launch over all babies / all giants:
+  //   1. per column one hoisted decomposition of ct1;
+  //   2. all baby key switches (one MAC, decomposition shared) and their
+  //      automorphisms with the + P*ct0 term (one launch);
+  //   3. all giant inner products sum_s pt * rot_s (lt_bsgs: each baby read
+  //      once and shared by every row), those of equal giant amount added
+  //      across the columns in the QP basis;
+  //   4. all giant key switches: ModDown of c1, decomposition, MAC with each
+  //      giant's key (+ c0 folded in), then the automorphism-accumulate;
+  //   5. ModDown of the accumulator.
+  // T0: the first member (the level, and a diagonal for the limb layout); cs:
+  // the cols inputs, one level, scale and batch.  keep_qp: where
+  // moddown_rescale would apply, step 5 is left out and the result holds the
+  // accumulator instead (Ciphertext::pend)
+  Ciphertext eval_layout(const LtLayout& Ly, const LinTrans& T0, const std::vector<const Ciphertext*>& cs,
+                         bool keep_qp) {
+    const lt_blocks::Plan& P = Ly.plan;
+    const int level = std::min(cs[0]->level, T0.level);
+    const int B = cs[0]->poly.B, RB = P.rows * B, nqp = level + 1 + K;
     const int beta = (level + 1 + K - 1) / K;
-    if (rescale && level < 1) throw std::runtime_error("cannot rescale a level-0 ciphertext");
     const int ng = (int)P.giants.size();
-    const LtRoute r = lt_route(env, tun, RB, level, P.nonzero_giants, rescale);
+    const LtRoute r = lt_route(env, tun, RB, level, P.nonzero_giants, keep_qp);
     const DecomposeRoute hoist = decompose_route(env, tun, 1, B, level);
     const std::vector<u64> pq = p_mod_q(level);
     // every key is looked up before anything is queued (galois_key throws)
@@ -2563,14 +2469,14 @@ struct Context {
       for (int b : col.babies)
         if (b) galois_key(galois_element(b), level);
 
-    // inner sums: comps [0, ng) = c0 of giant slot gs, [ng, 2 ng) = its c1; image i * B + b = row i
+    // inner sums: comps [0, ng) = c0 of giant slot gs, [ng, 2 ng) = its c1
     Poly Tt = alloc(2 * ng, nqp, RB);
     const LimbSet t0 = lsqp(Tt, 0, 1, level, level), t1 = lsqp(Tt, ng, 1, level, level);
     // (every plane of Tt is written: a row without diagonals for one of the
     // layer's giants has an entry with an empty mask in column 0's plan)
-    const Poly& pt0 = Ts[0]->diags.begin()->second.poly;
-    const LimbSet ptl = lsqp(pt0, 0, 1, level, Bk.level, 1);
-    for (int j = 0; j < C; ++j) {
+    const Poly& pt0 = T0.diags.begin()->second.poly;
+    const LimbSet ptl = lsqp(pt0, 0, 1, level, T0.level, 1);
+    for (int j = 0; j < P.cols; ++j) {
       const lt_blocks::Column& col = P.columns[j];
       const Ciphertext& ct = *cs[j];
       const int nb = (int)col.babies.size();
@@ -2604,9 +2510,10 @@ struct Context {
         }
         for (int k = 0; k < col.chunks; ++k) {
           const int e0 = lt_blocks::Plan::chunk_first(k, LT_MAXG), ne = lt_blocks::Plan::chunk_count(col, k, LT_MAXG);
-          // distinct bytes, as eval_lt's: the column's decomposition and ct once
-          // per row of the launch, each entry's output pair (read back when it
-          // accumulates), the baby keys and the entries' diagonals per QP limb
+          // distinct bytes: the column's decomposition (beta digits) and ct0/ct1
+          // once per row of the launch, each entry's output pair (read back when
+          // it accumulates), and per QP limb the baby keys (2 beta each) and the
+          // entries' diagonals, both shared by the batch
           const double lrows = (double)nqp * B;
           int npair = 0, nacc = 0;
           for (int e = e0; e < e0 + ne; ++e) {
@@ -2616,20 +2523,30 @@ struct Context {
           }
           Scope sc(this, P_LTMAC, 8.0 * N * (lrows * ((col.rotating ? beta : 0) + 2.0 + 2.0 * (ne + nacc)) +
                                              (double)nqp * (2.0 * beta * nrot + npair)));
-          if (orion_launch_lt_bsgs_col(t0, t1, dl, ctl, Bb, Bk.d_plan + Bk.first_chunk[j] + k, 0, ne, s0 > 0, ptl, d_tb,
-                                       N, B, stream))
-            throw std::runtime_error("lt_bsgs (column form) launch failed");
+          if (orion_launch_lt_bsgs(t0, t1, dl, ctl, Bb, Ly.d_plan + Ly.first_chunk[j], k, ne, s0 > 0,
+                                   P.rows * P.cols == 1, ptl, d_tb, N, B, stream))
+            throw std::runtime_error("lt_bsgs launch failed");
         }
       }
     }
-    Ciphertext all = lt_giant_steps(Tt, P.giants, level, RB, r, cs[0]->scale * (long double)mods[Bk.level]);
+    return lt_giant_steps(Tt, P.giants, level, RB, r, cs[0]->scale * (long double)mods[T0.level]);
+  }
+
+  // Blocked BSGS linear transform: out[i] = sum_j T[i][j](ct[j]), hoisted across
+  // rows and columns (eval_layout), then the rows cut from the batch.  Ts: the
+  // members (plans built).  rescale: the ModDown and the rescale as one division
+  // where moddown_rescale applies, the sequence elsewhere (the same bits).
+  std::vector<Ciphertext> eval_lt_blocks(const LtBlocks& Bk, const std::vector<LinTrans*>& Ts,
+                                         const std::vector<const Ciphertext*>& cs, bool rescale) {
+    if (rescale && std::min(cs[0]->level, Bk.level) < 1) throw std::runtime_error("cannot rescale a level-0 ciphertext");
+    const int B = cs[0]->poly.B;
+    Ciphertext all = eval_layout(Bk.lay, *Ts[0], cs, rescale);
     if (all.pend.buf)
       finish_moddown_rescale(all);
     else if (rescale)
       rescale_inplace(all);
-    // the rows, cut from the batch
     std::vector<Ciphertext> out;
-    for (int i = 0; i < R; ++i) {
+    for (int i = 0; i < Bk.rows; ++i) {
       std::vector<GatherSrc> src;
       gather_sources(all, i * B, B, src);
       Ciphertext o = new_ct(all.level, B, all.scale);
@@ -3071,25 +2988,11 @@ struct Context {
     T.level = level;
     T.ratio = 2;
     for (auto& kv : dm) T.idx.push_back(kv.first);
-    T.N1 = find_best_n1(T.idx, slots, 1);
-    std::set<int> seenb;
-    for (int d : T.idx) {
-      int gi, bi;
-      bsgs_split(d, slots, T.N1, &gi, &bi);
-      T.index[gi].push_back(bi);
-      if (!seenb.count(bi)) {
-        seenb.insert(bi);
-        T.babies.push_back(bi);
-      }
-    }
-    for (auto& kv : T.index) {
-      std::sort(kv.second.begin(), kv.second.end());
-      T.giants.push_back(kv.first);
-    }
+    const std::vector<int> giant_of = lt_bsgs_index(T, slots, 1);
     std::vector<cplx> vec(slots);
+    size_t k = 0;
     for (auto& kv : dm) {
-      int gi, bi;
-      bsgs_split(kv.first, slots, T.N1, &gi, &bi);
+      const int gi = giant_of[k++];
       for (int s2 = 0; s2 < slots; ++s2) vec[s2] = kv.second[((s2 - gi) % slots + slots) % slots];
       T.diags[kv.first & (slots - 1)] = encode_complex(vec, level, (long double)mods[level], true);
     }
@@ -3675,7 +3578,7 @@ static const bool g_hooks_set = [] {
   HandlePool<LtBlocks>::resolver() = res_ltbs;
   HandlePool<LtBlocks>::hook() = [](int o, unsigned long long b) { foreign_order(o, b, false); };
   HandlePool<LtBlocks>::hold() = [](const LtBlocks& b) {
-    if (t_act && t_act->capturing && b.dev) t_act->capture_holds.push_back(b.dev);
+    if (t_act && t_act->capturing && b.lay.dev) t_act->capture_holds.push_back(b.lay.dev);
   };
   HandlePool<Ciphertext>::hook() = [](int o, unsigned long long b) { foreign_order(o, b, true); };
   HandlePool<Plaintext>::hook() = [](int o, unsigned long long b) { foreign_order(o, b, false); };
@@ -3697,7 +3600,7 @@ static const bool g_hooks_set = [] {
       if (kv.second.poly.buf) t_act->capture_holds.push_back(kv.second.poly.buf);
     for (auto& kv : t.sdiags)
       if (kv.second.buf) t_act->capture_holds.push_back(kv.second.buf);
-    if (t.plan) t_act->capture_holds.push_back(t.plan);
+    if (t.lay.dev) t_act->capture_holds.push_back(t.lay.dev);
   };
   return true;
 }();
@@ -4734,6 +4637,23 @@ static int find_best_n1(const std::vector<int>& idx, int slots, int logMaxRatio)
   }
   return 1;
 }
+// the BSGS index of a new transform from its index list (T.idx) and log-ratio:
+// N1, the sorted giants, the babies in first-seen order; returns each
+// diagonal's giant amount
+static std::vector<int> lt_bsgs_index(LinTrans& T, int slots, int logRatio) {
+  T.N1 = find_best_n1(T.idx, slots, logRatio);
+  std::vector<int> giant_of;
+  std::set<int> gs, bs;
+  for (int d : T.idx) {
+    int gi, bi;
+    bsgs_split(d, slots, T.N1, &gi, &bi);
+    giant_of.push_back(gi);
+    gs.insert(gi);
+    if (bs.insert(bi).second) T.babies.push_back(bi);
+  }
+  T.giants.assign(gs.begin(), gs.end());
+  return giant_of;
+}
 
 int GenerateLinearTransform(int* diagIdx, int nIdx, float* data, int nData, int level, float ratio,
                             char* ioMode) {
@@ -4752,29 +4672,14 @@ int GenerateLinearTransform(int* diagIdx, int nIdx, float* data, int nData, int 
   T.idx.assign(diagIdx, diagIdx + nIdx);
   const int logRatio = (int)log((double)ratio);  // lineartransform.go:67 (natural log)
   if (logRatio < 0) throw std::runtime_error("naive (non-BSGS) linear transforms are not supported");
-  T.N1 = find_best_n1(T.idx, slots, logRatio);
-  std::set<int> seenb;
-  for (int d : T.idx) {
-    int gi, bi;
-    bsgs_split(d, slots, T.N1, &gi, &bi);
-    T.index[gi].push_back(bi);
-    if (!seenb.count(bi)) {
-      seenb.insert(bi);
-      T.babies.push_back(bi);
-    }
-  }
-  for (auto& kv : T.index) {
-    std::sort(kv.second.begin(), kv.second.end());
-    T.giants.push_back(kv.first);
-  }
+  const std::vector<int> giant_of = lt_bsgs_index(T, slots, logRatio);
   for (int r : T.giants)
     if (r) c.key_hint[c.galois_element(r)] = std::max(c.key_hint[c.galois_element(r)], level);
   for (int r : T.babies)
     if (r) c.key_hint[c.galois_element(r)] = std::max(c.key_hint[c.galois_element(r)], level);
   std::vector<float> vec(slots);
   for (int i = 0; i < nIdx && !load; ++i) {
-    int gi, bi;
-    bsgs_split(diagIdx[i], slots, T.N1, &gi, &bi);
+    const int gi = giant_of[i];
     const float* v = data + (size_t)i * slots;
     for (int s = 0; s < slots; ++s) vec[s] = v[((s - gi) % slots + slots) % slots];  // rotate right by giant
     T.diags[diagIdx[i] & (slots - 1)] = c.encode(vec.data(), slots, 1, level, (long double)c.mods[level], true);
@@ -4789,22 +4694,32 @@ int GetLinearTransformN1(int id) {
   API_END(-1)
 }
 
-// another context's transform whose plan is not built (its diagonals changed
-// after the pipelines were made): its owner builds it, under its lock -- only
-// a lower-index context may be waited on (lock order)
-static void foreign_plan(Context& c, LinTrans& T, int tid) {
-  Context* o = handle_ctx(tid);
-  if (T.plan_dirty && o && o != &c) {
-    if (o->index > c.index) throw std::runtime_error("linear transform " + std::to_string(tid) + " of pipeline " + std::to_string(o->index) + " has no device plan yet: evaluate it there first");
-    std::lock_guard<std::recursive_mutex> lk(o->mu);
-    if (T.plan_dirty) o->build_plan(T);
-  }
+// A device plan that is not built (the diagonals changed after the pipelines
+// were made) is built by the context that owns the handle, under its lock --
+// only a lower-index context may be waited on (lock order).  what: the kind of
+// handle, for the error
+static void owner_builds(Context& c, int id, const char* what, const std::function<void(Context&)>& build) {
+  Context* o = handle_ctx(id);
+  if (!o || o == &c) return build(c);
+  if (o->index > c.index)
+    throw std::runtime_error(std::string(what) + " " + std::to_string(id) + " of pipeline " +
+                             std::to_string(o->index) + " has no device plan yet: evaluate it there first");
+  std::lock_guard<std::recursive_mutex> lk(o->mu);
+  build(*o);
+}
+// a transform about to be evaluated: its diagonals loaded, its device plan built
+static void lt_ready(Context& c, LinTrans& T, int tid) {
+  c.lt_loaded(T);
+  if (T.plan_dirty)
+    owner_builds(c, tid, "linear transform", [&T](Context& o) {
+      if (T.plan_dirty) o.build_plan(T);
+    });
 }
 int EvaluateLinearTransform(int tid, int cid) {
   API_BEGIN
   Context& c = ctx();
   LinTrans& T = c.lts.get(tid);
-  foreign_plan(c, T, tid);
+  lt_ready(c, T, tid);
   Ciphertext r = c.eval_lt(T, c.cts.get(cid), true);
   const bool pend = (bool)r.pend.buf;
   const int rid = c.cts.add(std::move(r));
@@ -4830,9 +4745,7 @@ static std::vector<LinTrans*> blocks_members(Context& c, const LtBlocks& Bk, int
     if (!T || T->uid != Bk.uids[k])
       throw std::runtime_error("blocked linear transform " + std::to_string(bid) + ": its member transform " +
                                std::to_string(tid) + " has been deleted");
-    c.lt_loaded(*T);
-    foreign_plan(c, *T, tid);
-    if (T->plan_dirty) c.build_plan(*T);
+    lt_ready(c, *T, tid);
     Ts.push_back(T);
   }
   return Ts;
@@ -4859,8 +4772,8 @@ int OrionHipNewLinearTransformBlocks(const int* tids, int rows, int cols) {
     Bk.uids.push_back(T.uid);
     pairs.push_back(c.lt_pairs(T));
   }
-  Bk.plan = lt_blocks::plan(pairs, rows, cols, LT_MAXB, LT_MAXG, LT_MAXSLOT);
-  if (!Bk.plan.error.empty()) throw std::runtime_error(Bk.plan.error);
+  Bk.lay.plan = lt_blocks::plan(pairs, rows, cols, LT_MAXB, LT_MAXG, LT_MAXSLOT);
+  if (!Bk.lay.plan.error.empty()) throw std::runtime_error(Bk.lay.plan.error);
   c.build_blocks_plan(Bk, blocks_members(c, Bk, -1));
   return c.ltbs.add(std::move(Bk));
   API_END(-1)
@@ -4873,19 +4786,7 @@ int OrionHipEvaluateLinearTransformBlocks(int bid, const int* cids, int rescale,
   const std::vector<LinTrans*> Ts = blocks_members(c, Bk, bid);
   bool dirty = !Bk.built;
   for (size_t k = 0; k < Ts.size(); ++k) dirty = dirty || Ts[k]->rev != Bk.revs[k];
-  if (dirty) {
-    // (another context's blocks: its owner rebuilds them, as foreign_plan)
-    Context* o = handle_ctx(bid);
-    if (o && o != &c) {
-      if (o->index > c.index)
-        throw std::runtime_error("blocked linear transform " + std::to_string(bid) + " of pipeline " +
-                                 std::to_string(o->index) + " has no device plan yet: evaluate it there first");
-      std::lock_guard<std::recursive_mutex> lk(o->mu);
-      o->build_blocks_plan(Bk, Ts);
-    } else {
-      c.build_blocks_plan(Bk, Ts);
-    }
-  }
+  if (dirty) owner_builds(c, bid, "blocked linear transform", [&](Context& o) { o.build_blocks_plan(Bk, Ts); });
   // every source is looked up (and checked) before anything is allocated
   std::vector<const Ciphertext*> cs;
   for (int j = 0; j < Bk.cols; ++j) {

@@ -286,24 +286,18 @@ struct GatherTable {
   GatherSrc src[ORION_MAXGATHER];
 };
 
-// BSGS linear transform plan (device-resident, one per LinTrans): giants in
-// evaluation order, baby slots in the order of LinTrans::babies
-#define LT_MAXB 16   // baby rotations held in registers by one lt_bsgs launch
-#define LT_MAXG 64   // giants per plan
-#define LT_MAXSLOT 64
-struct LtPlan {
-  unsigned long long mask[LT_MAXG];      // bit s: giant g uses baby slot s
-  const u64* pt[LT_MAXG][LT_MAXSLOT];    // diagonal (QP plaintext) of (giant, slot), or null
-};
-// One chunk of a column's plan in a blocked transform (lt_blocks.h): entry e is
-// one (output row, giant) pair some block of the column has diagonals for.  Its
-// inner sum goes to component comp[e] (the giant's slot in the layer's giant
+// BSGS linear transform plan (device-resident): one chunk of a column's plan in
+// a blocked transform (lt_blocks.h; one transform is the 1 x 1 block).  Entry e
+// is one (output row, giant) pair some block of the column has diagonals for.
+// Its inner sum goes to component comp[e] (the giant's slot in the layer's giant
 // list) of the images row[e] * B .. row[e] * B + B - 1 of the inner-sum buffer;
 // acc[e]: an earlier column has written that plane, so this one adds to it.
-// mask and pt as LtPlan's, over the column's baby slots.
-struct LtColPlan {
-  unsigned long long mask[LT_MAXG];
-  const u64* pt[LT_MAXG][LT_MAXSLOT];
+#define LT_MAXB 16   // baby rotations held in registers by one lt_bsgs launch
+#define LT_MAXG 64   // entries per plan
+#define LT_MAXSLOT 64
+struct LtPlan {
+  unsigned long long mask[LT_MAXG];      // bit s: entry e uses baby slot s of the column
+  const u64* pt[LT_MAXG][LT_MAXSLOT];    // diagonal (QP plaintext) of (entry, slot), or the zero diagonal
   int comp[LT_MAXG], row[LT_MAXG], acc[LT_MAXG];
 };
 struct LtBabies {  // the baby steps of register slots [s0, s0 + nb) of one lt_bsgs launch

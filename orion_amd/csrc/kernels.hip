@@ -675,29 +675,33 @@ __device__ __forceinline__ void lt_xcd_decode(int& x, int& y, int& z) {
 // coefficient in registers and loops over the giants: the rotations never
 // touch HBM, and every diagonal (shared by the batch; the image index is the
 // fastest grid dimension) is read from L2.
-// PLAN = LtColPlan: the column form of a blocked transform.  The "giants" g0..g1
-// are the entries of one chunk of the column's plan, each with an output
-// component, an output row (images row * colB + bi; the grid spans colB images)
-// and its own accumulate flag -- all read from the plan at a uniform index, so
-// they stay in SGPRs.
-template <int MB, class PLAN>
+// The "giants" g0..g1 are the entries of one chunk of a column's plan
+// (lt_blocks.h; one transform is the 1 x 1 block), each with an output
+// component, an output row (images row * colB + bi; the grid spans the colB
+// images of the column's input) and its own accumulate flag -- all read from
+// the plan at a uniform index, so they stay in SGPRs.  t0 / t1: components 0
+// and ng of the layer's inner-sum buffer (batch rows * colB).
+// ONE: a chunk of a 1 x 1 layout, where the plan's comp, row and acc say
+// nothing new and are not read: entry g goes to component g - g0 of t0 / t1
+// (the components of the chunk's first entry), row 0, and no entry accumulates
+// but through `accumulate` (measured: profiles/r09a_lt_unify_ab.txt).
+template <int MB, bool ONE>
 __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const LimbSet& D, const LimbSet& ct,
-                                             const LtBabies& Bb, const PLAN* __restrict__ P, int g0, int g1,
+                                             const LtBabies& Bb, const LtPlan* __restrict__ P, int g0, int g1,
                                              int accumulate, const LimbSet& ptl, const DeviceTables* __restrict__ tb,
-                                             int N, int z0, int colB = 0) {
-  constexpr bool COL = std::is_same<PLAN, LtColPlan>::value;
+                                             int N, int z0, int colB) {
   // offset of entry g's output plane in t (t0 or t1), and whether the entry adds to it
   auto tgo = [&](const LimbSet& t, int g) -> long long {
-    if constexpr (COL)
-      return (long long)P->comp[g] * t.comp_stride + (long long)P->row[g] * colB * t.batch_stride;
-    else
+    if constexpr (ONE)
       return (long long)(g - g0) * t.comp_stride;
+    else
+      return (long long)P->comp[g] * t.comp_stride + (long long)P->row[g] * colB * t.batch_stride;
   };
   auto adds = [&](int g) -> bool {
-    if constexpr (COL)
-      return accumulate || P->acc[g];
-    else
+    if constexpr (ONE)
       return accumulate;
+    else
+      return accumulate || P->acc[g];
   };
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (Bb.xcd) lt_xcd_decode(bx, by, bz);
@@ -752,7 +756,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     // the giant loop instantiated with and without accumulation (uniform)
     auto giants = [&](auto acc_tag) {
       for (int g = g0; g < g1; ++g) {
-        const bool ACC = COL ? adds(g) : decltype(acc_tag)::value;  // (the column form: per entry, uniform)
+        const bool ACC = ONE ? decltype(acc_tag)::value : adds(g);  // (a layer's entries: per entry, uniform)
         const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
         const unsigned long long mask = P->mask[g] >> Bb.s0;
         u64 r0 = 0, r1 = 0;
@@ -785,7 +789,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
         t1.p[to1] = r1;
       }
     };
-    if (!COL && accumulate) giants(std::true_type{});
+    if (ONE && accumulate) giants(std::true_type{});
     else giants(std::false_type{});
     return;
   }
@@ -869,31 +873,19 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
   }
 }
 
-// MB = 8 at 4 waves per SIMD (<= 128 VGPRs); MB = 16 holds twice the babies
+// Entries e0 .. e1 - 1 of one plan chunk.  MB = 8 at 4 waves per SIMD (<= 128
+// VGPRs); MB = 16 holds twice the babies
+template <bool ONE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WAVES8)))
-lt_bsgs_kernel8(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int g0,
-                int g1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0) {
-  lt_bsgs_body<8, LtPlan>(t0, t1, D, ct, Bb, P, g0, g1, accumulate, ptl, tb, N, z0);
+lt_bsgs_kernel8(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int e0,
+                int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0, int colB) {
+  lt_bsgs_body<8, ONE>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB);
 }
+template <bool ONE>
 __global__ void __launch_bounds__(256)
-lt_bsgs_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int g0,
-                 int g1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0) {
-  lt_bsgs_body<16, LtPlan>(t0, t1, D, ct, Bb, P, g0, g1, accumulate, ptl, tb, N, z0);
-}
-// The column form of a blocked transform: entries e0 .. e1 - 1 of one chunk of
-// the column's plan (lt_bsgs_body with PLAN = LtColPlan).  t0 / t1: components
-// 0 and ng of the layer's inner-sum buffer (batch rows * colB); the grid's
-// images are the colB images of the column's input
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WAVES8)))
-lt_bsgs_col_kernel8(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtColPlan* __restrict__ P, int e0,
-                    int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int colB) {
-  lt_bsgs_body<8, LtColPlan>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, 0, colB);
-}
-__global__ void __launch_bounds__(256)
-lt_bsgs_col_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtColPlan* __restrict__ P,
-                     int e0, int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N,
-                     int colB) {
-  lt_bsgs_body<16, LtColPlan>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, 0, colB);
+lt_bsgs_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int e0,
+                 int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0, int colB) {
+  lt_bsgs_body<16, ONE>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB);
 }
 
 // Giant steps of a hoisted BSGS transform, key switches and accumulation fused:
@@ -1216,19 +1208,29 @@ int orion_launch_ks_mac(const LimbSet& out, const LimbSet& D, const LimbSet& own
   return 0;
 }
 
+// The first ne entries of chunk `chunk` of a column's plan (plan: the column's
+// first chunk).  t0 / t1: components 0 and ng of the inner-sum buffer, batch
+// rows * colB, every entry's row below rows; ct and D: the column's colB
+// images.  one: the layout is 1 x 1, so the chunk's entries are the components
+// from chunk * LT_MAXG on, in order (the ONE instantiation)
 int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
-                         const LtBabies& Bb, const LtPlan* plan, int g0, int g1, int accumulate, const LimbSet& ptl,
-                         const DeviceTables* tb, int N, hipStream_t st) {
-  if (Bb.nb < 1 || Bb.nb > LT_MAXB || g1 <= g0) return -1;
+                         const LtBabies& Bb, const LtPlan* plan, int chunk, int ne, int accumulate, bool one,
+                         const LimbSet& ptl, const DeviceTables* tb, int N, int colB, hipStream_t st) {
+  if (Bb.nb < 1 || Bb.nb > LT_MAXB || chunk < 0 || ne < 1 || ne > LT_MAXG) return -1;
+  if (colB < 1 || t0.nbatch % colB || ct.nbatch != colB || (one && t0.nbatch != colB)) return -1;
+  const LtPlan* P = plan + chunk;
+  LimbSet a0 = t0, a1 = t1;
+  if (one) a0.p += (long long)chunk * LT_MAXG * a0.comp_stride, a1.p += (long long)chunk * LT_MAXG * a1.comp_stride;
   auto launch = [&](int z0, int nz) {
     if (nz <= 0) return;
-    dim3 g(t0.nbatch, (N + 255) / 256, nz);
+    dim3 g(colB, (N + 255) / 256, nz);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, g, dim3(256), 0, st, a0, a1, D, ct, Bb, P, 0, ne, accumulate, ptl, tb, N, z0, colB);
+    };
     if (Bb.nb <= 8)
-      hipLaunchKernelGGL(lt_bsgs_kernel8, g, dim3(256), 0, st, t0, t1, D, ct, Bb, plan, g0, g1, accumulate, ptl, tb,
-                         N, z0);
+      one ? go(lt_bsgs_kernel8<true>) : go(lt_bsgs_kernel8<false>);
     else
-      hipLaunchKernelGGL(lt_bsgs_kernel16, g, dim3(256), 0, st, t0, t1, D, ct, Bb, plan, g0, g1, accumulate, ptl, tb,
-                         N, z0);
+      one ? go(lt_bsgs_kernel16<true>) : go(lt_bsgs_kernel16<false>);
   };
   // ORION_LT_SPLIT=1 (timing diagnostics): three launches, limb 0, the middle
   // Q limbs and the last Bb.K (P) limbs, so a kernel trace times each class
@@ -1240,23 +1242,6 @@ int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D,
   } else {
     launch(0, t0.nlimb);
   }
-  return 0;
-}
-
-// t0 / t1: batch rows * colB, every entry's row below rows; ct and D: the
-// column's colB images
-int orion_launch_lt_bsgs_col(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
-                             const LtBabies& Bb, const LtColPlan* plan, int e0, int e1, int accumulate,
-                             const LimbSet& ptl, const DeviceTables* tb, int N, int colB, hipStream_t st) {
-  if (Bb.nb < 1 || Bb.nb > LT_MAXB || e0 < 0 || e1 <= e0 || e1 > LT_MAXG) return -1;
-  if (colB < 1 || t0.nbatch % colB || ct.nbatch != colB) return -1;
-  dim3 g(colB, (N + 255) / 256, t0.nlimb);
-  if (Bb.nb <= 8)
-    hipLaunchKernelGGL(lt_bsgs_col_kernel8, g, dim3(256), 0, st, t0, t1, D, ct, Bb, plan, e0, e1, accumulate, ptl, tb,
-                       N, colB);
-  else
-    hipLaunchKernelGGL(lt_bsgs_col_kernel16, g, dim3(256), 0, st, t0, t1, D, ct, Bb, plan, e0, e1, accumulate, ptl, tb,
-                       N, colB);
   return 0;
 }
 

@@ -1,8 +1,9 @@
 // lt_blocks.h -- the layout of a blocked linear transform (an R x C matrix of
-// BSGS transforms evaluated as one call).  Host only: rotation amounts in, slot
-// and entry numbers out; no HIP, no device pointer, no Context.  backend.hip
-// fills the device plan (common.h LtColPlan) from this and decides nothing of
-// the layout itself.
+// BSGS transforms evaluated as one call).  A single transform is the 1 x 1
+// case: every linear transform the library evaluates is laid out here.  Host
+// only: rotation amounts in, slot and entry numbers out; no HIP, no device
+// pointer, no Context.  backend.hip fills the device plan (common.h LtPlan)
+// from this and decides nothing of the layout itself.
 //
 // The blocks of one layer have different N1, so everything is keyed by the
 // rotation amount.  Per column j the baby rotations of ct[j] are shared by all

@@ -114,6 +114,44 @@ static void check_band() {
   EXPECT(c.entries[64].diag[31] == 544 && c.entries[64].diag[0] == 545);
 }
 
+// One transform is the 1 x 1 block: one entry per giant, in the order of the
+// giant list, none accumulating.
+static void check_single() {
+  // range(65) + {2048} at N1 = 1: every diagonal its own giant, the one baby 0
+  std::vector<int> idx;
+  for (int d = 0; d <= 64; ++d) idx.push_back(d);
+  idx.push_back(2048);
+  const Plan P = plan({block(idx, 1)}, 1, 1, MAXB, MAXG, MAXSLOT);
+  EXPECT(P.error.empty());
+  EXPECT(P.giants.size() == 66 && P.giants.front() == 1 && P.giants[63] == 64 && P.giants[64] == 2048 && P.giants.back() == 0);
+  EXPECT(P.nonzero_giants == 65);
+  const Column& c = P.columns[0];
+  EXPECT((c.babies == std::vector<int>{0}));
+  EXPECT(c.entries.size() == 66 && c.chunks == 2 && c.passes == 1 && c.rotating == 0 && P.total_chunks == 2);
+  EXPECT(Plan::chunk_count(c, 0, MAXG) == 64 && Plan::chunk_count(c, 1, MAXG) == 2);
+  for (size_t k = 0; k < c.entries.size(); ++k) EXPECT(entry_is(c.entries[k], 0, (int)k, 1, 0));
+  // giant 1 is diagonal 1, giant 2048 the last of the list, giant 0 the first
+  EXPECT(c.entries[0].diag[0] == 1 && c.entries[64].diag[0] == 65 && c.entries[65].diag[0] == 0);
+
+  // the dense band range(768) at N1 = 32 alone: 24 giants, 32 babies in two passes
+  std::vector<int> band;
+  for (int d = 0; d < 768; ++d) band.push_back(d);
+  const Plan Q = plan({block(band, 32)}, 1, 1, MAXB, MAXG, MAXSLOT);
+  EXPECT(Q.error.empty());
+  const Column& q = Q.columns[0];
+  EXPECT(q.entries.size() == 24 && q.chunks == 1 && q.passes == 2 && q.rotating == 31);
+  for (size_t k = 0; k < q.entries.size(); ++k) EXPECT(entry_is(q.entries[k], 0, (int)k, 0xffffffffull, 0));
+
+  // no zero giant: 33 = 32 + 1, 65 = 64 + 1, 66 = 64 + 2 at N1 = 32; babies 1 (slot 0), 2 (slot 1)
+  const Plan S = plan({block({33, 65, 66}, 32)}, 1, 1, MAXB, MAXG, MAXSLOT);
+  EXPECT(S.error.empty());
+  EXPECT((S.giants == std::vector<int>{32, 64}) && S.nonzero_giants == 2);
+  const Column& s = S.columns[0];
+  EXPECT((s.babies == std::vector<int>{1, 2}) && s.rotating == 2 && s.entries.size() == 2);
+  EXPECT(entry_is(s.entries[0], 0, 0, 1, 0) && entry_is(s.entries[1], 0, 1, 3, 0));
+  EXPECT(s.entries[1].diag[0] == 1 && s.entries[1].diag[1] == 2 && s.entries[0].diag[1] == -1);
+}
+
 static void check_refusals() {
   std::vector<Pair> wide;
   for (int b = 0; b <= 64; ++b) wide.push_back({0, b});  // 65 distinct babies
@@ -133,6 +171,7 @@ static void check_refusals() {
 int main() {
   check_2x3();
   check_band();
+  check_single();
   check_refusals();
   if (g_fail) {
     printf("%d checks failed\n", g_fail);

@@ -6,7 +6,8 @@ The reference is a restatement of the call's definition (include/orion_hip.h)
 from the oracle's primitives -- gadget product, automorphism, coefficient
 product, ModDown, rescale -- and numpy modular additions, fed with the
 library's exported diagonals and Galois keys; with one column each row must
-also be bit-equal to its own EvaluateLinearTransform."""
+also be bit-equal to its own EvaluateLinearTransform (the 1 x 1 block: the
+same code, so those tests hold both sides against the restatement too)."""
 import numpy as np
 import pytest
 
@@ -20,6 +21,8 @@ IDX_2X3 = [[BIG, [0], [5, 64, 128, 192]],
            [[1, 2, 3], [64, 128, 4000], BIG]]
 N1_2X3 = [[32, 1, 128], [2, 256, 32]]
 BAND = list(range(768))
+# one baby (amount 0) and 66 giants, 65 of them rotating: N1 = 1 at any ratio
+MANY_GIANTS = list(range(65)) + [2048]
 
 
 @pytest.fixture(scope="module")
@@ -42,9 +45,9 @@ _cache = SchemeCache()
 BSGS_RATIO = 4.0
 
 
-def _gen(lib, rng, idx, level):
+def _gen(lib, rng, idx, level, ratio=BSGS_RATIO):
     diags = rng.uniform(-1, 1, (len(idx), lib.slots)).astype(np.float32)
-    return lib.GenerateLinearTransform(idx, list(diags.reshape(-1)), level, BSGS_RATIO, "none"), diags
+    return lib.GenerateLinearTransform(idx, list(diags.reshape(-1)), level, ratio, "none"), diags
 
 
 @pytest.fixture
@@ -66,8 +69,10 @@ def env(torch_cuda, oracle_mod):
             band=[[_gen(lib, rng, BAND, 1)] for _ in range(3)],
             zero=[[_gen(lib, rng, [0], 3), _gen(lib, rng, [0], 3)]],
             other_level=_gen(lib, rng, [0, 1], 2),
+            many_giants=_gen(lib, rng, MANY_GIANTS, 1, ratio=1e9),
         )
-        every = [t for k in ("m23", "band", "zero") for row in lts[k] for t, _ in row] + [lts["other_level"][0]]
+        every = [t for k in ("m23", "band", "zero") for row in lts[k] for t, _ in row]
+        every += [lts["other_level"][0], lts["many_giants"][0]]
         gels = sorted({g for t in every for g in lib.GetLinearTransformRotationKeys(t)})
         lib.GenerateConsolidatedRotationKeys(gels)
         return lib, orc, lts
@@ -207,15 +212,22 @@ def test_2x3_matches_the_definition(env, rescale):
 def test_1x1_is_evaluate_linear_transform(env):
     lib, orc, lts = env
     t = lts["m23"][0][0][0]
-    ct = lib.import_ciphertext(_planted(lib, 3, 2, 20), SCALE)
+    x = _planted(lib, 3, 2, 20)
+    ct = lib.import_ciphertext(x, SCALE)
     blk = lib.new_linear_transform_blocks([[t]])
+    ref = Restated(lib, orc, 3)
+    mem = [[(t, BIG, lib.GetLinearTransformN1(t))]]
     for rescale in (0, 1):
         one = lib.EvaluateLinearTransform(t, ct)
         if rescale:
             lib.Rescale(one)
         (out,) = lib.evaluate_linear_transform_blocks(blk, [ct], rescale=rescale)
-        assert np.array_equal(lib.export_ciphertext(out), lib.export_ciphertext(one)), rescale
+        got = lib.export_ciphertext(one)
+        assert np.array_equal(lib.export_ciphertext(out), got), rescale
         assert lib.GetCiphertextScaleF(out) == lib.GetCiphertextScaleF(one)
+        for b in (0, 1):  # (both calls run the same code: the restatement is the witness)
+            (exp,) = ref.blocks([x[b]], mem, rescale)
+            assert np.array_equal(got[b], exp), (rescale, b)
         _delete(lib, [one, out])
     lib.delete_linear_transform_blocks(blk)
     _delete(lib, [ct])
@@ -224,19 +236,42 @@ def test_1x1_is_evaluate_linear_transform(env):
 def test_3x1_band_two_baby_passes_two_chunks(env):
     """Three blocks of the dense band range(768): N1 = 32, 24 giants and 32
     babies each -- two passes of 16 register slots, 72 (row, giant) entries in
-    two plan chunks of 64; one column, so each row is its own transform."""
+    two plan chunks of 64; one column, so each row is its own transform.  Row 0
+    is also held against the restatement (a single transform is the 1 x 1 block:
+    both calls run the same code; its 768 diagonals cost the restatement about
+    1.3 s of CPU)."""
     lib, orc, lts = env
     rows = lts["band"]
     assert all(lib.GetLinearTransformN1(t) == 32 for (t, _), in rows)
-    ct = lib.import_ciphertext(_planted(lib, 1, 1, 21), SCALE)
+    x = _planted(lib, 1, 1, 21)
+    ct = lib.import_ciphertext(x, SCALE)
     blk = lib.new_linear_transform_blocks(_ids(rows))
     outs = lib.evaluate_linear_transform_blocks(blk, [ct], rescale=0)
+    (exp,) = Restated(lib, orc, 1).blocks([x[0]], [[(rows[0][0][0], BAND, 32)]], 0)
+    assert np.array_equal(lib.export_ciphertext(outs[0])[0], exp)
     for i, ((t, _),) in enumerate(rows):
         one = lib.EvaluateLinearTransform(t, ct)
         assert np.array_equal(lib.export_ciphertext(outs[i]), lib.export_ciphertext(one)), i
         _delete(lib, [one])
     lib.delete_linear_transform_blocks(blk)
     _delete(lib, [ct] + outs)
+
+
+def test_single_transform_with_two_plan_chunks(env):
+    """One baby (amount 0) and 66 giants, 65 of them rotating -- more than the
+    64 entries of a plan chunk and the 64 giants of a giant-phase launch: two
+    plan chunks in the baby phase, partial sums in the giant phase.  (The
+    restatement: about 0.3 s of CPU.)"""
+    lib, orc, lts = env
+    t, _ = lts["many_giants"]
+    # (GenerateLinearTransform truncates ln(1e9) to 20; the ratio never reaches 2^20)
+    assert lib.GetLinearTransformN1(t) == 1 == orc.find_best_bsgs_n1(MANY_GIANTS, 20)
+    x = _planted(lib, 1, 1, 22)
+    ct = lib.import_ciphertext(x, SCALE)
+    one = lib.EvaluateLinearTransform(t, ct)
+    (exp,) = Restated(lib, orc, 1).blocks([x[0]], [[(t, MANY_GIANTS, 1)]], 0)
+    assert np.array_equal(lib.export_ciphertext(one)[0], exp)
+    _delete(lib, [ct, one])
 
 
 def test_1x2_without_a_rotating_giant(env):
