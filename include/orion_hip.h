@@ -337,7 +337,9 @@ void OrionHipDeleteLinearTransformBlocks(int blocks);
 /* GPU encoder with device-resident slots (e.g. a torch tensor's data_ptr):
  * dvalues [batch][lenPerImage] float32; DecodeDevice writes the real parts of
  * all slots, [batch][N/2] float64, to device memory (asynchronous);
- * DecodeF64 returns them to the host as float64 (Decode casts to float32) */
+ * DecodeF64 returns them to the host as float64 (Decode casts to float32).
+ * Encode, EncodeBatch and EncodeBatchDevice refuse a scale that is not finite
+ * and positive ("scale must be finite and positive", handle -1) */
 int EncodeBatchDevice(const float *dvalues, int lenPerImage, int batch, int level, double scale);
 int DecodeDevice(int pt, double *dout);
 int DecodeF64(int pt, double *out, unsigned long n);

@@ -5,7 +5,10 @@ import this module.  The product path (orion_amd/) never does.
 
 Restates Lattigo-v6 RNS-CKKS arithmetic reached from
 /root/reference/orion/backend/lattigo/*.go (see ckks_oracle.h for the
-function-by-function citations).  Parity with Lattigo itself is unpinned.
+function-by-function citations).  Parity with Lattigo itself is unpinned;
+encode and decode are held to the canonical embedding and to the fixed-point
+rule in plain Python (tests/test_oracle.py, helpers.canonical_slots and
+helpers.fixed_point_rule).
 """
 import ctypes
 import os

@@ -4249,10 +4249,15 @@ void LoadSecretKey(char* data, unsigned long len) {
 
 // ---- encoder / encryptor ----
 void NewEncoder(void) {}
+// enc_crt_kernel converts |x| * scale + 0.5 to u64: defined only for a finite scale > 0
+static void check_encode_scale(double scale) {
+  if (!(scale > 0) || !std::isfinite(scale)) throw std::runtime_error("scale must be finite and positive");
+}
 int Encode(float* values, int n, int level, unsigned long scale) {
   API_BEGIN
   Context& c = ctx();
   if (level < 0 || level >= c.L) throw std::runtime_error("invalid level");
+  check_encode_scale((double)scale);
   return c.pts.add(c.encode(values, n, 1, level, (long double)scale, false));
   API_END(-1)
 }
@@ -4260,6 +4265,7 @@ int EncodeBatch(float* values, int n, int B, int level, unsigned long scale) {
   API_BEGIN
   Context& c = ctx();
   if (level < 0 || level >= c.L || B < 1) throw std::runtime_error("invalid level/batch");
+  check_encode_scale((double)scale);
   return c.pts.add(c.encode(values, n, B, level, (long double)scale, false));
   API_END(-1)
 }
@@ -4267,6 +4273,7 @@ int EncodeBatchDevice(const float* dvalues, int n, int B, int level, double scal
   API_BEGIN
   Context& c = ctx();
   if (level < 0 || level >= c.L || B < 1 || !dvalues) throw std::runtime_error("invalid level/batch/pointer");
+  check_encode_scale(scale);
   return c.pts.add(c.encode_dev(dvalues, n, B, level, (long double)scale, false));
   API_END(-1)
 }

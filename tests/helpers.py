@@ -149,6 +149,155 @@ def constant_rows(xs, qs, N):
     return out
 
 
+def bsgs_split(d, slots, n1):
+    """(giant, baby) step of diagonal d under baby-step count n1 (Lattigo's BSGSIndex)"""
+    rot = d & (slots - 1)
+    return ((rot // n1) * n1) & (slots - 1), rot & (n1 - 1)
+
+
+# ---- the encoder's fixed-point rule, restated (enc_crt_kernel, csrc/encoder.hip) ----
+def fixed_point_y(c, scale):
+    """the float64 product the rule rounds: the float32 slot value times the scale"""
+    return np.float64(np.float32(c)) * np.float64(scale)
+
+
+def fixed_point_rule(c, scale):
+    """The integer a coefficient of value c (float32) takes at `scale`, as a
+    Python int: with y = fl(c * scale) and a = |y|, k = (u64)(a + 0.5) with the
+    addition in float64 for a < 2^64, the integer a itself above that (a double
+    that large is an integer); the sign of y goes back on."""
+    y = fixed_point_y(c, scale)
+    a = abs(y)
+    assert np.isfinite(a)
+    k = int(np.float64(a) + np.float64(0.5)) if a < 2.0 ** 64 else int(a)
+    return -k if y < 0 else k
+
+
+def encode_planted_cases(qs, q60):
+    """[(name, c, scale)], c >= 0: slot values and scales whose product y sits
+    on an edge of the fixed-point rule (each is planted with both signs of c).
+    qs: the chain's Q primes (q_0 the first prime, q_1 a 40-bit one); q60: a
+    60-bit first prime.  With c = 1, y is the scale; the cases with another c
+    reach the same y through an integer scale below 2^64, the only kind the
+    host calls (Encode, EncodeBatch: unsigned long) take."""
+    q1 = qs[1]
+    assert abs(q1 - 2 ** 40) < 2 ** 30 and abs(q60 - 2 ** 60) < 2 ** 50  # primes close to 2^40, 2^60
+    one = [
+        # zero
+        ("zero", 0.0, 2.0 ** 40), ("tiny", float(np.float32(1e-20)), 2.0 ** 40), ("pred(1/2)", 1.0, float(np.nextafter(0.5, 0.0))),
+        ("1/2", 1.0, 0.5),
+        # ties k + 1/2
+        ("1+1/2", 1.0, 1.5), ("2+1/2", 1.0, 2.5), ("2^23+1/2", 1.0, 2.0 ** 23 + 0.5),
+        ("2^51-1+1/2", 1.0, 2.0 ** 51 - 0.5),
+        # integers of [2^52, 2^53): y + 0.5 is itself a tie; an odd y comes back as y + 1
+        ("2^52+2", 1.0, 2.0 ** 52 + 2), ("2^52+1", 1.0, 2.0 ** 52 + 1), ("2^52+12345", 1.0, 2.0 ** 52 + 12345),
+        ("2^53-3", 1.0, 2.0 ** 53 - 3), ("2^53-1", 1.0, 2.0 ** 53 - 1), ("2^53", 1.0, 2.0 ** 53),
+        ("2^53+2", 1.0, 2.0 ** 53 + 2),
+        # the top of the one-word path, the start of the big path (mant * 2^e, e >= 12)
+        ("2^63-1024", 1.0, 2.0 ** 63 - 1024), ("2^63", 1.0, 2.0 ** 63), ("2^63+2048", 1.0, 2.0 ** 63 + 2048),
+        ("2^64-2048", 1.0, 2.0 ** 64 - 2048), ("2^64", 1.0, 2.0 ** 64), ("2^64+4096", 1.0, 2.0 ** 64 + 4096),
+        ("(2^53-1)2^12", 1.0, float((2 ** 53 - 1) << 12)), ("3*2^70", 1.0, 3 * 2.0 ** 70),
+        ("1.5*2^200", 1.0, 1.5 * 2.0 ** 200), ("(2^53-1)2^900", 1.0, float((2 ** 53 - 1) << 900)),
+        # modulus edges: exact doubles; the negative sign of a multiple gives residue 0, not q
+        ("q1", 1.0, float(q1)), ("2q1", 1.0, float(2 * q1)), ("q1-1", 1.0, float(q1 - 1)), ("q1+1", 1.0, float(q1 + 1)),
+        ("fl(q0)", 1.0, float(qs[0])), ("fl(q60)", 1.0, float(q60)),
+        # the same edges through an integer scale
+        ("1/2 host", 0.5, 1.0), ("1+1/2 host", 0.5, 3.0), ("2^23+1/2 host", 0.5, 2.0 ** 24 + 1),
+        ("2^51-1+1/2 host", 0.5, 2.0 ** 52 - 1), ("2^64 host", 2.0, 2.0 ** 63), ("2^64+4096 host", 2.0, 2.0 ** 63 + 2048),
+        ("(2^53-1)2^12 host", 4096.0, 2.0 ** 53 - 1), ("3*2^70 host", 2.0 ** 40, 3 * 2.0 ** 30),
+    ]
+    for name, c, scale in one:
+        assert float(np.float32(c)) == c and np.isfinite(scale), name
+    # control: the product itself rounds (24-bit c times a 53-bit scale near 2^40)
+    rng = np.random.default_rng(4040)
+    for i in range(16):
+        c = float(np.float32(rng.uniform(0.25, 4.0)))
+        one.append((f"random {i}", c, float(int(rng.integers(2 ** 52, 2 ** 53))) * 2.0 ** -12))
+    return one
+
+
+def host_scale(scale):
+    """True if the host calls can carry `scale` (an integer in [1, 2^64))"""
+    return 1.0 <= scale < 2.0 ** 64 and scale == int(scale)
+
+
+def planted_batches(cases):
+    """{scale: [(name, +-c)]}: both signs of every c, the slot values that share a
+    scale in one batch (more than one image per call)"""
+    out = {}
+    for name, c, scale in cases:
+        out.setdefault(scale, []).extend([(name, c), (f"-({name})", -c)])
+    return out
+
+
+# ---- the canonical embedding, by definition, in extended precision ----
+_PI_LD = np.longdouble("3.14159265358979323846264338327950288")
+
+
+def canonical_slots(m, js, ci):
+    """Real parts of slots js of the integer polynomial m (N Python ints or an
+    int64 array, centred coefficients), as numpy longdouble.  Standard ring:
+    slot j = sum_k m_k cos(2 pi (k 5^j mod 2N) / 2N); ConjugateInvariant ring:
+    m_0 + 2 sum_{k >= 1} m_k cos(2 pi (k 5^j mod 4N) / 4N).  k 5^j is reduced
+    as an integer before the conversion."""
+    N = len(m)
+    M = 4 * N if ci else 2 * N
+    coef = np.array([int(x) for x in m], dtype=np.int64).astype(np.longdouble)
+    if ci:
+        coef[1:] *= 2
+    k = np.arange(N, dtype=np.int64)
+    out = np.zeros(len(js), dtype=np.longdouble)
+    for i, j in enumerate(js):
+        e = (k * pow(5, int(j), M)) % M  # < 2^34: exact in int64
+        out[i] = np.sum(coef * np.cos(2 * _PI_LD * e.astype(np.longdouble) / np.longdouble(M)))
+    return out
+
+
+def embedding_slots(n, rng):
+    """the slots the embedding tests evaluate: the ends, the middle, 10 random ones"""
+    return [0, 1, 2, n // 2 - 1, n // 2, n - 1] + [int(x) for x in rng.integers(0, n, 10)]
+
+
+# the deviation of decode from canonical_slots allowed (coefficients +-2^45 at
+# scale 2^40, slots of a few thousand).  Measured on the CPU oracle
+# (test_decode_matches_canonical_embedding): 2.8e-12 (Standard 2^13), 2.1e-12
+# (CI 2^13), 3.9e-12 (Standard 2^15), 4.3e-12 (CI 2^15): over 20x the worst of
+# them and thirteen orders under the slots, so a wrong root, order or conjugate
+# fails by thousands
+EMBED_TOL = 1e-10
+
+# the chain of the encode/decode tests at every FFT split (no keys)
+SPLIT_CHAIN = dict(logq=[60, 40, 40], logp=[60])
+
+
+def embedding_plaintext(orc, seed):
+    """(m, rows): signed coefficients uniform in +-2^45 (int64 [N]) and their
+    level-1 NTT rows [2][N] under orc's chain"""
+    rng = np.random.default_rng(seed)
+    m = rng.integers(-2 ** 45, 2 ** 45 + 1, orc.N, dtype=np.int64)
+    rows = np.stack([orc.ntt(j, np.array([int(x) % orc.moduli[j] for x in m], dtype=np.uint64)) for j in range(2)])
+    return m, rows
+
+
+def centred_coeffs(orc, row0):
+    """the centred integer coefficients (int64) of NTT row 0 of a plaintext"""
+    q = orc.moduli[0]
+    a = orc.intt(0, row0)
+    return np.where(a > q // 2, a.astype(np.int64) - np.int64(q), a.astype(np.int64))
+
+
+def split_images(slots, nvals, seed):
+    """3 float32 images of nvals slots: uniform in (-3, 3) with +-4 planted at
+    slots 0, 1, slots/2 and nvals - 1 (where the image has them)"""
+    rng = np.random.default_rng(seed)
+    v = rng.uniform(-3, 3, (3, nvals)).astype(np.float32)
+    for b in range(3):
+        for t, s in enumerate((0, 1, slots // 2, nvals - 1)):
+            if s < nvals:
+                v[b, s] = 4.0 if (t + b) % 2 else -4.0
+    return v
+
+
 SMALL = dict(logn=13, logq=[55, 40, 40, 40, 40, 40], logp=[60, 60])
 
 # the chains (and levels) of the planted basis-extension parity tests

@@ -11,7 +11,7 @@ same code, so those tests hold both sides against the restatement too)."""
 import numpy as np
 import pytest
 
-from tests.helpers import SMALL, SchemeCache, plant_runs, rand_ct
+from tests.helpers import SMALL, SchemeCache, bsgs_split, plant_runs, rand_ct
 
 pytestmark = pytest.mark.gpu
 
@@ -90,11 +90,6 @@ def _addmod(a, b, q):
     return np.where(s >= q, s - q, s)
 
 
-def _split(d, slots, n1):
-    rot = d & (slots - 1)
-    return ((rot // n1) * n1) & (slots - 1), rot & (n1 - 1)
-
-
 class Restated:
     def __init__(self, lib, orc, level):
         self.lib, self.orc, self.level = lib, orc, level
@@ -146,7 +141,7 @@ class Restated:
             t = {}  # giant amount -> [c0, c1]
             for j, (lt, idx, n1) in enumerate(row):
                 for d in idx:
-                    g, b = _split(d, lib.slots, n1)
+                    g, b = bsgs_split(d, lib.slots, n1)
                     if b not in rots[j]:
                         rots[j][b] = self.baby(xs[j], b)
                     pt = lib.export_lt_diagonal(lt, d, level)

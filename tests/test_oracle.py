@@ -7,7 +7,9 @@ import os
 import numpy as np
 import pytest
 
-from tests.helpers import PLANT_CHAINS, constant_rows, decode_edge_values, digit_limbs, plant_digit_values
+from tests.helpers import (EMBED_TOL, PLANT_CHAINS, SPLIT_CHAIN, canonical_slots, constant_rows, decode_edge_values,
+                           digit_limbs, embedding_plaintext, embedding_slots, encode_planted_cases, fixed_point_rule,
+                           fixed_point_y, plant_digit_values, planted_batches)
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -702,3 +704,112 @@ def test_decode_of_constant_is_the_rounded_integer(oracle_mod, name, level, ci):
         for b, x in enumerate(xs):
             got = orc.decode(rows[b], level, scale)
             assert got.shape == (orc.slots,) and np.all(got == float(x) / scale), (x, scale, got[0])
+
+
+# ---- the encoder's fixed-point rule on planted edges (CPU guards of tests/test_gpu_encode_planted.py) ----
+def _planted_encode_oracle(oracle_mod, name, ci):
+    p = PLANT_CHAINS[name]
+    mods = oracle_mod.gen_moduli(p["logn"] + ci, p["logq"], p["logp"])
+    q60 = oracle_mod.gen_moduli(14, [60], [])[0]
+    return oracle_mod.Oracle(8, mods, len(p["logq"]), len(p["logp"]), ci=ci), encode_planted_cases(mods, q60)
+
+
+@pytest.mark.parametrize("name,ci", [("small", False), ("small", True), ("k1", False)])
+def test_planted_encode_matches_the_rule(oracle_mod, name, ci):
+    """An image whose every slot is c encodes to the constant polynomial
+    rule(fl(c * scale)): the special iFFT's sums double, its differences are
+    zero, and n c (1/n) is exact.  The oracle's encode against the Python
+    restatement of the fixed-point rule (helpers.fixed_point_rule), exact
+    integers, on every planted (c, scale) with both signs; chains with a 55-bit
+    and a 60-bit first prime, both rings (the rule does not depend on the degree)."""
+    orc, cases = _planted_encode_oracle(oracle_mod, name, ci)
+    level = 5
+    qs, mods = orc.moduli[:level + 1], list(range(level + 1))
+    assert len({n for n, _, _ in cases}) == len(cases)
+    for scale, imgs in planted_batches(cases).items():
+        for nm, c in imgs:
+            got = orc.encode(np.full(orc.slots, np.float64(np.float32(c))), scale, mods)
+            exp = constant_rows([fixed_point_rule(c, scale)], qs, orc.N)[0]
+            assert np.array_equal(got, exp), (nm, c, scale, got[:, 0], exp[:, 0])
+
+
+def _frac(y):
+    from fractions import Fraction
+    return Fraction(float(abs(y)))
+
+
+# wrong rules a planted case must tell from the right one: (y, q) -> residue
+def _signed(k, y, q):
+    return (-k if y < 0 else k) % q
+
+
+def _wrong_exact_floor(y, q):  # floor(|y| + 1/2) in exact arithmetic
+    from fractions import Fraction
+    return _signed(int(_frac(y) + Fraction(1, 2)), y, q)
+
+
+def _wrong_truncate(y, q):
+    return _signed(int(_frac(y)), y, q)
+
+
+def _wrong_half_even(y, q):
+    return _signed(round(_frac(y)), y, q)  # Fraction.__round__: ties to even
+
+
+def _right(y, q):
+    a = abs(float(y))
+    return _signed(int(np.float64(a) + np.float64(0.5)) if a < 2.0 ** 64 else int(a), y, q)
+
+
+def _wrong_negative_zero_is_q(y, q):
+    r = _right(y, q)
+    return q if y < 0 and r == 0 else r
+
+
+def _wrong_one_word_ends_at_2_63(y, q):
+    """'The big path from 2^63'.  Read literally (a >= 2^63 takes int(a))
+    that is the right rule: a + 0.5 == a in float64 from 2^53 on, and
+    mant * 2^11 is as exact as mant * 2^12.  What a threshold at 2^63 gets
+    wrong is the one-word conversion it is there for, a signed one, which
+    saturates at 2^63 - 1 while the exact path still starts at 2^64."""
+    a = abs(float(y))
+    if 2.0 ** 63 <= a < 2.0 ** 64:
+        return _signed(2 ** 63 - 1, y, q)
+    return _right(y, q)
+
+
+def test_planted_encode_cases_have_teeth(oracle_mod):
+    """Each plausible wrong fixed-point rule disagrees with the right one on at
+    least one planted case (with the chain's residues, as the parity tests
+    compare them), and the rule of this test is the rule of helpers.py."""
+    orc, cases = _planted_encode_oracle(oracle_mod, "small", False)
+    qs = orc.moduli[:6]
+    ys = []
+    for scale, imgs in planted_batches(cases).items():
+        for nm, c in imgs:
+            ys.append((nm, fixed_point_y(c, scale)))
+            assert [_right(ys[-1][1], q) for q in qs] == [fixed_point_rule(c, scale) % q for q in qs], nm
+    for wrong in (_wrong_exact_floor, _wrong_truncate, _wrong_half_even, _wrong_negative_zero_is_q,
+                  _wrong_one_word_ends_at_2_63):
+        caught = [nm for nm, y in ys if [wrong(y, q) for q in qs] != [_right(y, q) for q in qs]]
+        print(wrong.__name__, caught)
+        assert caught, wrong.__name__
+
+
+# ---- decode against the canonical embedding evaluated directly (np.longdouble) ----
+@pytest.mark.parametrize("logn,ci", [(13, False), (13, True), (15, False), (15, True)])
+def test_decode_matches_canonical_embedding(oracle_mod, logn, ci):
+    """Slot j of a decoded plaintext is m(zeta^(5^j)) / scale, zeta the
+    primitive 2N-th root (4N-th on the ConjugateInvariant ring): the oracle's
+    special FFT against helpers.canonical_slots, a direct sum in extended
+    precision, on signed coefficients uniform in +-2^45 at scale 2^40."""
+    mods = oracle_mod.gen_moduli(logn + ci, SPLIT_CHAIN["logq"], SPLIT_CHAIN["logp"])
+    orc = oracle_mod.Oracle(logn, mods, 3, 1, ci=ci)
+    m, rows = embedding_plaintext(orc, 500 + logn)
+    js = embedding_slots(orc.slots, np.random.default_rng(logn))
+    exp = canonical_slots(m, js, ci) / np.longdouble(2.0 ** 40)
+    got = orc.decode(rows, 1, 2.0 ** 40)
+    dev = float(np.abs(got[js].astype(np.longdouble) - exp).max())
+    print(f"logn {logn} ci {ci}: max |slot| {float(np.abs(exp).max()):.3g}, deviation {dev:.3g}")
+    assert float(np.abs(exp).max()) > 100
+    assert dev <= EMBED_TOL, dev
