@@ -67,6 +67,13 @@
 #ifndef LT_PRESPLIT
 #define LT_PRESPLIT 1
 #endif
+// images per lt_bsgs workgroup that share one staged copy of the diagonals
+#define LT_IW 4
+// 0 (timing builds only): launches of 4 images and more keep the
+// one-image-per-workgroup mapping
+#ifndef LT_SHARED
+#define LT_SHARED 1
+#endif
 
 namespace {
 
@@ -685,11 +692,29 @@ __device__ __forceinline__ void lt_xcd_decode(int& x, int& y, int& z) {
 // nothing new and are not read: entry g goes to component g - g0 of t0 / t1
 // (the components of the chunk's first entry), row 0, and no entry accumulates
 // but through `accumulate` (measured: profiles/r09a_lt_unify_ab.txt).
-template <int MB, bool ONE>
+// IW: images per workgroup.  1: a workgroup is 256 coefficients of one image
+// (grid: colB images x N / 256 blocks x limbs).  4: a workgroup is 64
+// coefficients of 4 images, wave w on image 4 bx + w (grid: ceil(colB / 4) x
+// N / 64 x limbs, exact: N % 64 == 0).  A diagonal word depends on the
+// coefficient and not on the image, so per giant the workgroup loads the MB
+// diagonal rows of its 64 coefficients once -- wave w the rows s = w (mod 4),
+// into `lds` (2 x MB x 64 words) -- and every wave reads its lane's MB words
+// from there.  Two buffers: the rows of giant g + 1 are loaded before giant
+// g's products and stored to LDS after them, so one barrier per giant orders
+// both the stores to a buffer before its reads and the reads before the next
+// stores.  That store waits for the two loads with vmcnt(0), so it stands
+// before the giant's own two stores to t0 / t1: behind them it waited for
+// their completion too, every giant (lt_bsgs 4.86 against 4.76 ms per step,
+// profiles/r10a_lt_shared_diag_ab.txt).
+// No thread leaves before the last barrier: a wave past the batch (colB % 4
+// != 0) stages its rows like the others and skips its own loads, products and
+// stores.  The arithmetic and its order are those of IW = 1.
+template <int MB, bool ONE, int IW>
 __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const LimbSet& D, const LimbSet& ct,
                                              const LtBabies& Bb, const LtPlan* __restrict__ P, int g0, int g1,
                                              int accumulate, const LimbSet& ptl, const DeviceTables* __restrict__ tb,
-                                             int N, int z0, int colB) {
+                                             int N, int z0, int colB, u64* lds) {
+  static_assert(IW == 1 || (kBlk / IW == 64 && MB % IW == 0), "one wave per image, the rows dealt out evenly");
   // offset of entry g's output plane in t (t0 or t1), and whether the entry adds to it
   auto tgo = [&](const LimbSet& t, int g) -> long long {
     if constexpr (ONE)
@@ -705,10 +730,16 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
   };
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (Bb.xcd) lt_xcd_decode(bx, by, bz);
-  const int bi = bx;
-  const int n = by * kBlk + threadIdx.x;
+  constexpr int CW = kBlk / IW;  // coefficients per workgroup
+  const int wv = IW > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / CW) : 0;
+  const int lane = IW > 1 ? (int)threadIdx.x % CW : (int)threadIdx.x;
+  const int bi = IW > 1 ? bx * IW + wv : bx;
+  const int n = by * CW + lane;
   const int l = z0 + bz;
-  if (n >= N) return;
+  if constexpr (IW == 1) {
+    if (n >= N) return;
+  }
+  const bool active = bi < colB;  // wave-uniform; IW = 1: the grid has colB images
   const int m = arg_byte(t0.mod, l);
   const ModConst mc = tb->mc[m];
   const bool isq = l <= Bb.level;
@@ -726,7 +757,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
 #pragma unroll
   for (int s = 0; s < MB; ++s) {
     x0[s] = x1[s] = 0;
-    if (s < Bb.nb) {
+    if (s < Bb.nb && (IW == 1 || active)) {
       if (Bb.key[s] && !(LT_ABLATE & 2) && !((LT_ABLATE & 8) && mc.bar_k > 48)) {
         const int j = jx[s];
         u64 r0, r1;
@@ -743,6 +774,47 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
       }
     }
   }
+  // IW > 1, the staged diagonals: diag_first before a giant loop, then per
+  // giant diag (pv[s] = slot Bb.s0 + s at this thread's coefficient) before
+  // its products and diag_next after them.  (IW = 1 loads pv in the loop.)
+  constexpr int RW = IW > 1 ? MB / IW : 1;  // rows a wave stages per giant
+  u64 stg[RW];
+  int cur = 0;
+  auto fetch = [&](int g) {
+    const unsigned long long mask = P->mask[g] >> Bb.s0;
+#pragma unroll
+    for (int k = 0; k < RW; ++k) {
+      const int s = wv + IW * k;
+      stg[k] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+    }
+  };
+  auto put = [&](int buf) {
+#pragma unroll
+    for (int k = 0; k < RW; ++k) lds[(buf * MB + wv + IW * k) * CW + lane] = stg[k];
+  };
+  auto diag_first = [&]() {
+    if constexpr (IW > 1) {
+      if (g0 < g1) {
+        fetch(g0);
+        put(0);
+      }
+    }
+  };
+  auto diag = [&](int g, u64(&pv)[MB]) {
+    // (after the last giant: its own rows again, into the buffer nobody reads.
+    // Without a branch round the loads and the stores to LDS the compiler
+    // counts the loads in flight, and waits for these two only)
+    fetch(g + 1 < g1 ? g + 1 : g);
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < MB; ++s) pv[s] = lds[(cur * MB + s) * CW + lane];
+  };
+  auto diag_next = [&](int g) {
+    if constexpr (IW > 1) {
+      cur ^= 1;
+      put(cur);
+    }
+  };
   const bool small = mc.bar_k <= 48;  // block-uniform
   if (small) {
     // < 2^48 moduli: float64 split products (MacD), one reduction per giant;
@@ -755,18 +827,27 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     }
     // the giant loop instantiated with and without accumulation (uniform)
     auto giants = [&](auto acc_tag) {
+      diag_first();
       for (int g = g0; g < g1; ++g) {
         const bool ACC = ONE ? decltype(acc_tag)::value : adds(g);  // (a layer's entries: per entry, uniform)
         const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
         const unsigned long long mask = P->mask[g] >> Bb.s0;
         u64 r0 = 0, r1 = 0;
-        if (ACC) {
+        if (ACC && (IW == 1 || active)) {
           r0 = t0.p[to0];
           r1 = t1.p[to1];
         }
         u64 pv[MB];
+        if constexpr (IW == 1) {
 #pragma unroll
-        for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+          for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+        } else {
+          diag(g, pv);
+          if (!active) {
+            diag_next(g);
+            continue;
+          }
+        }
         MacD a0, a1;
         macd_zero(a0), macd_zero(a1);
 #pragma unroll
@@ -785,6 +866,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
         const u64 v0 = macd_reduce(a0, mc), v1 = macd_reduce(a1, mc);
         r0 = ACC ? add_mod(r0, v0, mc.q) : v0;
         r1 = ACC ? add_mod(r1, v1, mc.q) : v1;
+        diag_next(g);
         t0.p[to0] = r0;
         t1.p[to1] = r1;
       }
@@ -803,17 +885,26 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
 #pragma unroll
       for (int s = 0; s < MB; ++s) x0[s] = split30(x0[s]), x1[s] = split30(x1[s]);
     }
+    diag_first();
     for (int g = g0; g < g1; ++g) {
       const unsigned long long mask = P->mask[g] >> Bb.s0;
       u64 r0 = 0, r1 = 0;
       const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
-      if (adds(g)) {
+      if (adds(g) && (IW == 1 || active)) {
         r0 = t0.p[to0];
         r1 = t1.p[to1];
       }
       u64 pv[MB];
+      if constexpr (IW == 1) {
 #pragma unroll
-      for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+        for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+      } else {
+        diag(g, pv);
+        if (!active) {
+          diag_next(g);
+          continue;
+        }
+      }
       MacW a0, a1;
       macw_zero(a0), macw_zero(a1);
 #pragma unroll
@@ -834,6 +925,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
           macw_zero(a0), macw_zero(a1);
         }
       }
+      diag_next(g);
       t0.p[to0] = r0;
       t1.p[to1] = r1;
     }
@@ -841,19 +933,28 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
   }
   // moduli of at most 60 bits: 8 products per reduction (mac_reduce8)
   const bool acc8 = LT_INT_ACC8 && mc.bar_k <= 60;
+  diag_first();
   for (int g = g0; g < g1; ++g) {
     const unsigned long long mask = P->mask[g] >> Bb.s0;
     u64 r0 = 0, r1 = 0;
     const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
-    if (adds(g)) {
+    if (adds(g) && (IW == 1 || active)) {
       r0 = t0.p[to0];
       r1 = t1.p[to1];
     }
     // issue every diagonal load of this giant before the first product so
     // their latencies overlap (the branches are wave-uniform)
     u64 pv[MB];
+    if constexpr (IW == 1) {
 #pragma unroll
-    for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+      for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+    } else {
+      diag(g, pv);
+      if (!active) {
+        diag_next(g);
+        continue;
+      }
+    }
     MacAcc a0, a1;
     mac_zero(a0), mac_zero(a1);
 #pragma unroll
@@ -868,6 +969,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
         mac_zero(a0), mac_zero(a1);
       }
     }
+    diag_next(g);
     t0.p[to0] = r0;
     t1.p[to1] = r1;
   }
@@ -879,13 +981,31 @@ template <bool ONE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WAVES8)))
 lt_bsgs_kernel8(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int e0,
                 int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0, int colB) {
-  lt_bsgs_body<8, ONE>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB);
+  lt_bsgs_body<8, ONE, 1>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB, nullptr);
 }
 template <bool ONE>
 __global__ void __launch_bounds__(256)
 lt_bsgs_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P, int e0,
                  int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0, int colB) {
-  lt_bsgs_body<16, ONE>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB);
+  lt_bsgs_body<16, ONE, 1>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB, nullptr);
+}
+// The same with LT_IW images per workgroup, the diagonals staged in LDS once
+// for all of them (lt_bsgs_body, IW > 1)
+template <bool ONE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WAVES8)))
+lt_bsgs_shared_kernel8(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P,
+                       int e0, int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N, int z0,
+                       int colB) {
+  __shared__ u64 lds[2 * 8 * (256 / LT_IW)];
+  lt_bsgs_body<8, ONE, LT_IW>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB, lds);
+}
+template <bool ONE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
+lt_bsgs_shared_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies Bb, const LtPlan* __restrict__ P,
+                        int e0, int e1, int accumulate, LimbSet ptl, const DeviceTables* __restrict__ tb, int N,
+                        int z0, int colB) {
+  __shared__ u64 lds[2 * 16 * (256 / LT_IW)];
+  lt_bsgs_body<16, ONE, LT_IW>(t0, t1, D, ct, Bb, P, e0, e1, accumulate, ptl, tb, N, z0, colB, lds);
 }
 
 // Giant steps of a hoisted BSGS transform, key switches and accumulation fused:
@@ -1221,13 +1341,22 @@ int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D,
   const LtPlan* P = plan + chunk;
   LimbSet a0 = t0, a1 = t1;
   if (one) a0.p += (long long)chunk * LT_MAXG * a0.comp_stride, a1.p += (long long)chunk * LT_MAXG * a1.comp_stride;
+  // LT_IW images and more: a workgroup is 64 coefficients of LT_IW images and
+  // loads their diagonals once (its grid must be exact: the kernel has barriers
+  // and no bounds check)
+  const bool shared = LT_SHARED && colB >= LT_IW && N % (256 / LT_IW) == 0;
   auto launch = [&](int z0, int nz) {
     if (nz <= 0) return;
-    dim3 g(colB, (N + 255) / 256, nz);
+    const dim3 g = shared ? dim3((colB + LT_IW - 1) / LT_IW, N / (256 / LT_IW), nz) : dim3(colB, (N + 255) / 256, nz);
     auto go = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, g, dim3(256), 0, st, a0, a1, D, ct, Bb, P, 0, ne, accumulate, ptl, tb, N, z0, colB);
     };
-    if (Bb.nb <= 8)
+    if (shared) {
+      if (Bb.nb <= 8)
+        one ? go(lt_bsgs_shared_kernel8<true>) : go(lt_bsgs_shared_kernel8<false>);
+      else
+        one ? go(lt_bsgs_shared_kernel16<true>) : go(lt_bsgs_shared_kernel16<false>);
+    } else if (Bb.nb <= 8)
       one ? go(lt_bsgs_kernel8<true>) : go(lt_bsgs_kernel8<false>);
     else
       one ? go(lt_bsgs_kernel16<true>) : go(lt_bsgs_kernel16<false>);
