@@ -334,6 +334,46 @@ int OrionHipNewLinearTransformBlocks(const int *transforms, int rows, int cols);
 int OrionHipEvaluateLinearTransformBlocks(int blocks, const int *cts, int rescale, int *out);
 void OrionHipDeleteLinearTransformBlocks(int blocks);
 
+/* A sum of ciphertext products with one relinearisation: sum_i a[i] * b[i]
+ * (a squared norm, a dot product of encrypted vectors held as several
+ * ciphertexts, attention-style scores).  Relinearisation is linear in the
+ * degree-2 component, so one tensor pass accumulates (D0, D1, D2) over all n
+ * pairs and one key switch of D2 follows, where the loop of
+ * MulRelinCiphertextNew / AddCiphertext calls runs n key switches.  ModDown of
+ * a sum is not the sum of ModDowns, so the result differs in its last bits from
+ * that loop; it has its own exact definition:
+ *
+ *   level = the minimum level over all 2n operands; B = the operands' common
+ *   batch: each operand has batch B or 1, and a one-image operand is broadcast,
+ *   as in MulRelinCiphertextNew.  For every limb j <= level, mod q_j:
+ *     D0  = sum_i a[i].c0 b[i].c0
+ *     D1  = sum_i (a[i].c0 b[i].c1 + a[i].c1 b[i].c0)
+ *     D2  = sum_i a[i].c1 b[i].c1
+ *     out = (D0, D1) + KeySwitch_rlk(D2)      (the gadget product, then ModDown)
+ *   scale = a[0].scale * b[0].scale, as a long double product.
+ *
+ * Every pair's product scale must be bit-equal to that one: the library does
+ * not match scales on the caller's behalf (the rule of
+ * OrionHipStackCiphertexts).  With n = 1 the result is bit-equal to
+ * MulRelinCiphertextNew(a[0], b[0]).  The result is a new handle of the calling
+ * thread's context and behaves like MulRelinCiphertextNew's: a Rescale or
+ * RescaleNew that follows as the next call runs with the ModDown as one
+ * division by P q_level, and gives the bits of the rescaled definition.
+ *
+ * A handle may appear any number of times and on both sides; a pair with
+ * a[i] == b[i] is a square (its two rows are read once).  A pending deferred
+ * op runs first; an operand of another context is read like any foreign
+ * operand; after one warm call the call may be captured into a graph (the pair
+ * table travels in the kernel arguments).  The tensor pass runs as
+ * ceil(n / 16) launches.
+ *
+ * Errors: -1 and OrionHipLastError for a null pointer, n < 1, an unknown
+ * handle, no relinearisation key, operands whose batches differ (and are not
+ * 1), a pair whose product scale differs (the pair's index, the handles and
+ * both values are named), and a poisoned source (its poison message).  A
+ * failed call allocates no handle. */
+int OrionHipMulRelinSum(const int *a, const int *b, int n);
+
 /* GPU encoder with device-resident slots (e.g. a torch tensor's data_ptr):
  * dvalues [batch][lenPerImage] float32; DecodeDevice writes the real parts of
  * all slots, [batch][N/2] float64, to device memory (asynchronous);

@@ -173,6 +173,7 @@ SIGNATURES = {
     "OrionHipNewLinearTransformBlocks": ([P(c_int), c_int, c_int], c_int),
     "OrionHipEvaluateLinearTransformBlocks": ([c_int, P(c_int), c_int, P(c_int)], c_int),
     "OrionHipDeleteLinearTransformBlocks": ([c_int], None),
+    "OrionHipMulRelinSum": ([P(c_int), P(c_int), c_int], c_int),
     "ImportCiphertext": ([P(c_ulong), c_int, c_int, c_double], c_int),
     "ExportCiphertext": ([c_int, P(c_ulong), c_ulong], c_int),
     "ImportPlaintext": ([P(c_ulong), c_int, c_int, c_double], c_int),
@@ -553,6 +554,17 @@ class HipLibrary:
         """Free a blocked transform (its member transforms stay)."""
         self.lib.OrionHipDeleteLinearTransformBlocks(int(blocks))
         self._blocks_shape.pop(int(blocks), None)
+
+    def mul_relin_sum(self, a_handles, b_handles):
+        """sum_i a[i] * b[i] with one relinearisation (OrionHipMulRelinSum): one
+        new handle at the operands' lowest level; every pair's product scale
+        must be the same.  A handle may repeat, and a[i] == b[i] is a square."""
+        a, b = [int(h) for h in a_handles], [int(h) for h in b_handles]
+        if len(a) != len(b):
+            raise ValueError(f"mul_relin_sum: {len(a)} a operands and {len(b)} b operands")
+        self.lib.OrionHipClearError()
+        h = self.lib.OrionHipMulRelinSum((c_int * len(a))(*a), (c_int * len(b))(*b), len(a))
+        return self._chk(h, "OrionHipMulRelinSum")
 
     # Device-pointer calls run asynchronously on the library stream, which
     # torch does not know about: order them against the tensor's stream both

@@ -29,6 +29,7 @@
 #include "hostmath.h"
 #include "lt_blocks.h"
 #include "ntt_route.h"
+#include "tensor_sum.h"
 #include "wire.h"
 
 int orion_launch_ntt(int logN, const LimbSet& s, const DeviceTables* tb, bool inverse, hipStream_t st);
@@ -41,6 +42,8 @@ int orion_launch_ew(int op, const LimbSet& o, const LimbSet& a, const LimbSet& b
                     const DeviceTables* tb, int N, hipStream_t st);
 int orion_launch_tensor(const LimbSet& d, const LimbSet& a, const LimbSet& b, const DeviceTables* tb, int N,
                         hipStream_t st);
+int orion_launch_tensor_sum(const LimbSet& d, const tsum::Table& T, bool acc, const DeviceTables* tb, int N,
+                            hipStream_t st);
 int orion_launch_gather(u64* dst, long long d_comp, long long d_limb, int nimg, int nlimb, const GatherTable& T,
                         int N, hipStream_t st);
 int orion_launch_basis_ext(const LimbSet& out, const LimbSet& in, const BasisExtTable* T, const DeviceTables* tb,
@@ -2169,6 +2172,48 @@ struct Context {
     const bool pend = r.end == KsEnd::KeepQP;
     Ciphertext out = pend ? pending_ct(level, B, a.scale * b.scale) : new_ct(level, B, a.scale * b.scale);
     // (d0, d1) + keyswitch(d2): the addition is folded into the gadget product
+    keyswitch(r, lsq(d, 2, 1, level), level, B, rlk, L - 1, pend ? out.pend : out.poly, d.ptr(),
+              d.ptr() + d.comp_stride());
+    return out;
+  }
+
+  // sum_i a[i] x b[i] with one relinearisation (tensor_sum.h): one tensor pass
+  // accumulates (d0, d1, d2) over all pairs, ORION_MAXTSUM pairs per launch,
+  // then mul_relin's tail.  The operands' batches are B or 1 (checked by the
+  // caller); level = the minimum over the operands.  keep_qp: as eval_lt's
+  Ciphertext mul_relin_sum(const std::vector<const Ciphertext*>& a, const std::vector<const Ciphertext*>& b, int level,
+                           int B, long double scale, bool keep_qp = false) {
+    if (!have_rlk) throw std::runtime_error("relinearization key not generated");
+    const int n = (int)a.size();
+    if (n < 1 || b.size() != a.size()) throw std::runtime_error("a sum of products needs as many a as b operands");
+    Poly d = alloc(3, level + 1, B);
+    const LimbSet ld = lsq(d, 0, 3, level);
+    for (int c = 0; c < tsum::launches(n); ++c) {
+      const int first = tsum::chunk_first(c), cnt = tsum::chunk_count(n, c);
+      tsum::Table T;
+      memset(&T, 0, sizeof(T));
+      // the squares first (a pair of one buffer: two rows to read, not four),
+      // each kind in the caller's order
+      for (int sq = 1; sq >= 0; --sq) {
+        for (int i = first; i < first + cnt; ++i) {
+          const Poly &pa = a[i]->poly, &pb = b[i]->poly;
+          if ((pa.ptr() == pb.ptr()) != (bool)sq) continue;
+          tsum::Pair& e = T.pr[T.n++];
+          e.a = pa.ptr(), e.a_comp = pa.comp_stride(), e.a_limb = pa.limb_stride();
+          e.a_batch = pa.B == 1 && B > 1 ? 0 : pa.batch_stride();
+          e.b = pb.ptr(), e.b_comp = pb.comp_stride(), e.b_limb = pb.limb_stride();
+          e.b_batch = pb.B == 1 && B > 1 ? 0 : pb.batch_stride();
+        }
+        if (sq) T.nsq = T.n;
+      }
+      // distinct bytes per limb-image: 4 rows per pair (2 for a square), the 3
+      // outputs, and d read back by every launch after the first
+      Scope sc(this, P_TENSOR, 8.0 * N * (level + 1) * B * (4 * (cnt - T.nsq) + 2 * T.nsq + 3 + (c ? 3 : 0)));
+      if (orion_launch_tensor_sum(ld, T, c > 0, d_tb, N, stream)) throw std::runtime_error("tensor sum launch failed");
+    }
+    const KeySwitchRoute r = ks_route(B, level, 0, keep_qp);
+    const bool pend = r.end == KsEnd::KeepQP;
+    Ciphertext out = pend ? pending_ct(level, B, scale) : new_ct(level, B, scale);
     keyswitch(r, lsq(d, 2, 1, level), level, B, rlk, L - 1, pend ? out.pend : out.poly, d.ptr(),
               d.ptr() + d.comp_stride());
     return out;
@@ -4612,6 +4657,54 @@ int MulRelinCiphertextNew(int a, int b) {
   API_BEGIN
   Context& c = ctx();
   Ciphertext r = c.mul_relin(c.cts.get(a), c.cts.get(b), true);
+  const bool pend = (bool)r.pend.buf;
+  const int rid = c.cts.add(std::move(r));
+  if (pend) defer_apply(c, {deferral::Ev::OpenModDown, rid});
+  return rid;
+  API_END(-1)
+}
+// sum_i a[i] x b[i], relinearised once (orion_hip.h; Context::mul_relin_sum)
+int OrionHipMulRelinSum(const int* a, const int* b, int n) {
+  API_BEGIN
+  Context& c = ctx();
+  if (!a || !b) throw std::runtime_error("null handle list");
+  if (n < 1)
+    throw std::runtime_error("cannot sum " + std::to_string(n) + " ciphertext products: at least one pair is needed");
+  if (!c.have_rlk) throw std::runtime_error("relinearization key not generated");
+  // every operand is looked up (and checked) before anything is allocated; an
+  // operand of another context orders this stream after its producer (cts.get)
+  std::vector<const Ciphertext*> A(n), Bv(n);
+  std::vector<std::shared_ptr<Buffer>> keep;  // the operands' buffers, until the launches are queued
+  int level = 0, B = 1, bid = -1;
+  long double scale = 0;
+  for (int i = 0; i < n; ++i) {
+    A[i] = &c.cts.get(a[i]);
+    Bv[i] = &c.cts.get(b[i]);
+    for (int side = 0; side < 2; ++side) {
+      const Ciphertext& x = side ? *Bv[i] : *A[i];
+      const int id = side ? b[i] : a[i];
+      if (!x.poly.ptr() || x.poly.ncomp < 2 || x.poly.nlimb < x.level + 1)
+        throw std::runtime_error("ciphertext " + std::to_string(id) + " holds no degree-1 polynomial pair");
+      level = i == 0 && side == 0 ? x.level : std::min(level, x.level);
+      if (x.poly.B != 1) {
+        if (B != 1 && x.poly.B != B)
+          throw std::runtime_error("cannot sum products of ciphertexts " + std::to_string(bid) + " (batch " +
+                                   std::to_string(B) + ") and " + std::to_string(id) + " (batch " +
+                                   std::to_string(x.poly.B) + "): the batches differ");
+        if (B == 1) B = x.poly.B, bid = id;
+      }
+      keep.push_back(x.poly.buf);
+    }
+    const long double si = A[i]->scale * Bv[i]->scale;
+    if (i == 0)
+      scale = si;
+    else if (si != scale)
+      throw std::runtime_error("cannot sum ciphertext products: pair " + std::to_string(i) + " (" +
+                               std::to_string(a[i]) + " x " + std::to_string(b[i]) + ") has scale " + scale_str(si) +
+                               ", pair 0 (" + std::to_string(a[0]) + " x " + std::to_string(b[0]) + ") has scale " +
+                               scale_str(scale) + ": the scales differ");
+  }
+  Ciphertext r = c.mul_relin_sum(A, Bv, level, B, scale, true);
   const bool pend = (bool)r.pend.buf;
   const int rid = c.cts.add(std::move(r));
   if (pend) defer_apply(c, {deferral::Ev::OpenModDown, rid});

@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "ntt2s_rows.h"
+#include "tensor_sum.h"
 
 // timing-only ablation of lt_bsgs (0 in the product): bit 0 skips the giant
 // inner products of moduli below 2^48, bit 1 skips the baby gadget products,
@@ -215,6 +216,101 @@ __global__ void __launch_bounds__(256) tensor_kernel(LimbSet d, LimbSet a, LimbS
   *(ulonglong2*)(d.p + row_off(d, 0, l, bi) + n) = d0;
   *(ulonglong2*)(d.p + row_off(d, 1, l, bi) + n) = d1;
   *(ulonglong2*)(d.p + row_off(d, 2, l, bi) + n) = d2;
+}
+
+// A sum of ct x ct tensors (tensor_sum.h): d0 = sum a0 b0, d1 = sum (a0 b1 +
+// a1 b0), d2 = sum a1 b1 over the T.n pairs of the launch; ACC: added to the d
+// an earlier launch wrote.  tensor_kernel's layout (two coefficients per
+// thread, 16-B accesses, grid y = (limb, image)); the pair table is read from
+// the kernel arguments with wave-uniform indices (scalar loads).  Memory-bound:
+// per limb-image 8 N (4 n + 3) bytes, 8 N (2 n + 3) when every pair is a
+// square.  The loads of two pairs are issued before the first product; the
+// squares (two rows each, not four) have a loop of their own, so that no load
+// sits under a per-pair branch.  The products are summed unreduced and reduced
+// every tsum::interval pairs (once per launch on moduli of at most 52 bits).
+struct TsumRows {
+  ulonglong2 a0, a1, b0, b1;
+};
+template <bool SQ>
+__device__ __forceinline__ TsumRows tsum_load(const tsum::Pair& p, int l, int bi, int n) {
+  TsumRows r;
+  const u64* pa = p.a + l * p.a_limb + bi * p.a_batch + n;
+  r.a0 = *(const ulonglong2*)pa;
+  r.a1 = *(const ulonglong2*)(pa + p.a_comp);
+  if (!SQ) {
+    const u64* pb = p.b + l * p.b_limb + bi * p.b_batch + n;
+    r.b0 = *(const ulonglong2*)pb;
+    r.b1 = *(const ulonglong2*)(pb + p.b_comp);
+  }
+  return r;
+}
+template <bool SQ>
+__device__ __forceinline__ void tsum_mac(tsum::Acc3& sx, tsum::Acc3& sy, const TsumRows& r) {
+  if (SQ) {
+    tsum::mac_square(sx, r.a0.x, r.a1.x);
+    tsum::mac_square(sy, r.a0.y, r.a1.y);
+  } else {
+    tsum::mac_pair(sx, r.a0.x, r.a1.x, r.b0.x, r.b1.x);
+    tsum::mac_pair(sy, r.a0.y, r.a1.y, r.b0.y, r.b1.y);
+  }
+}
+struct TsumState {
+  tsum::Acc3 sx, sy;  // the unreduced sums of the thread's two coefficients
+  u64 x0, x1, x2, y0, y1, y2;  // the reduced sums so far: (d0, d1, d2) of either coefficient
+  int held;                    // pairs in sx, sy
+};
+__device__ __forceinline__ void tsum_flush(TsumState& s, const tsum::Mod& mc) {
+  tsum::flush(s.sx, mc, s.x0, s.x1, s.x2);
+  tsum::flush(s.sy, mc, s.y0, s.y1, s.y2);
+  s.held = 0;
+}
+// the pairs [first, end) of the table, two at a time and an odd one last
+template <bool SQ>
+__device__ __forceinline__ void tsum_run(TsumState& s, const tsum::Table& T, int first, int end, int l, int bi, int n,
+                                         const tsum::Mod& mc) {
+  int i = first;
+  for (; i + 1 < end; i += 2) {
+    const TsumRows r0 = tsum_load<SQ>(T.pr[i], l, bi, n), r1 = tsum_load<SQ>(T.pr[i + 1], l, bi, n);
+    if (tsum::due(s.held, 2, mc)) tsum_flush(s, mc);
+    tsum_mac<SQ>(s.sx, s.sy, r0);
+    tsum_mac<SQ>(s.sx, s.sy, r1);
+    s.held += 2;
+  }
+  if (i < end) {
+    const TsumRows r0 = tsum_load<SQ>(T.pr[i], l, bi, n);
+    if (tsum::due(s.held, 1, mc)) tsum_flush(s, mc);
+    tsum_mac<SQ>(s.sx, s.sy, r0);
+    s.held += 1;
+  }
+}
+template <bool ACC>
+__global__ void __launch_bounds__(256) tensor_sum_kernel(LimbSet d, tsum::Table T,
+                                                         const DeviceTables* __restrict__ tb, int N) {
+  const int row = blockIdx.y;
+  const int bi = row % d.nbatch;
+  const int l = row / d.nbatch;
+  const int n = (blockIdx.x * kBlk + threadIdx.x) * 2;
+  if (n >= N) return;
+  // (read through the pointer: a copy of the whole ModConst would live in scratch)
+  const tsum::Mod mc = tsum::mod_of(tb->mc[arg_byte(d.mod, l)]);
+  ulonglong2* p0 = (ulonglong2*)(d.p + row_off(d, 0, l, bi) + n);
+  ulonglong2* p1 = (ulonglong2*)(d.p + row_off(d, 1, l, bi) + n);
+  ulonglong2* p2 = (ulonglong2*)(d.p + row_off(d, 2, l, bi) + n);
+  TsumState s;
+  tsum::zero(s.sx);
+  tsum::zero(s.sy);
+  s.held = 0;
+  s.x0 = s.x1 = s.x2 = s.y0 = s.y1 = s.y2 = 0;
+  if (ACC) {
+    const ulonglong2 e0 = *p0, e1 = *p1, e2 = *p2;
+    s.x0 = e0.x, s.y0 = e0.y, s.x1 = e1.x, s.y1 = e1.y, s.x2 = e2.x, s.y2 = e2.y;
+  }
+  tsum_run<true>(s, T, 0, T.nsq, l, bi, n, mc);
+  tsum_run<false>(s, T, T.nsq, T.n, l, bi, n, mc);
+  tsum_flush(s, mc);
+  *p0 = make_ulonglong2(s.x0, s.y0);
+  *p1 = make_ulonglong2(s.x1, s.y1);
+  *p2 = make_ulonglong2(s.x2, s.y2);
 }
 
 // Exact basis extension (Lattigo ModUpExact restated; the
@@ -1236,6 +1332,20 @@ int orion_launch_tensor(const LimbSet& d, const LimbSet& a, const LimbSet& b, co
                         hipStream_t st) {
   const int rows = d.nlimb * d.nbatch;
   hipLaunchKernelGGL(tensor_kernel, ew_grid(N, rows), dim3(256), 0, st, d, a, b, tb, N);
+  return 0;
+}
+
+// d (3 components) = (acc ? d : 0) + the tensors of T's pairs
+int orion_launch_tensor_sum(const LimbSet& d, const tsum::Table& T, bool acc, const DeviceTables* tb, int N,
+                            hipStream_t st) {
+  const int rows = d.nlimb * d.nbatch;
+  if (T.n < 1 || T.n > ORION_MAXTSUM || T.nsq < 0 || T.nsq > T.n || d.ncomp != 3 || rows < 1 || rows > 65535 || N < 2 ||
+      (N & 1))
+    return -1;
+  if (acc)
+    hipLaunchKernelGGL(tensor_sum_kernel<true>, ew_grid(N, rows), dim3(256), 0, st, d, T, tb, N);
+  else
+    hipLaunchKernelGGL(tensor_sum_kernel<false>, ew_grid(N, rows), dim3(256), 0, st, d, T, tb, N);
   return 0;
 }
 
