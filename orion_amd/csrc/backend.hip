@@ -1059,10 +1059,7 @@ struct Context {
     io.src = src;
     return io;
   }
-#ifndef ORION_NTT_DEFAULT_ORDER
-#define ORION_NTT_DEFAULT_ORDER 2
-#endif
-  int ntt_order = getenv("ORION_NTT_ORDER") ? atoi(getenv("ORION_NTT_ORDER")) : ORION_NTT_DEFAULT_ORDER;
+  int ntt_order = getenv("ORION_NTT_ORDER") ? atoi(getenv("ORION_NTT_ORDER")) : 2;
   // launch routes (ntt_route.h): the switches, and what init_moduli knows
   const NttTuning tun = NttTuning::from_env();
   NttEnv env;
@@ -1129,23 +1126,21 @@ struct Context {
     }
     fio.ifuse = 1;
     fio.imid = iio.dst;
-    if (r.tgroup) {
-      // segments: runs of target limbs on the same basis-extension table (the
-      // same source limbs; the rescale prep has one source), at most G each
-      int k = 0;
-      for (int l = 0; l < fio.dst.nlimb;) {
-        int e = l + 1;
-        while (e < fio.dst.nlimb && e - l < r.tgroup &&
-               (fio.pro != NTT_PRO_BEXT || fio.bx_tab[e] == fio.bx_tab[l]))
-          ++e;
-        fio.tg_l0[k] = (unsigned char)l;
-        fio.tg_n[k] = (unsigned char)(e - l);
-        ++k;
-        l = e;
-      }
-      fio.ntg = k;
-      fio.tgroup = r.tgroup;
+    // segments: runs of target limbs on the same basis-extension table (the
+    // same source limbs; the rescale prep has one source), at most tgroup each
+    int k = 0;
+    for (int l = 0; l < fio.dst.nlimb;) {
+      int e = l + 1;
+      while (e < fio.dst.nlimb && e - l < r.tgroup &&
+             (fio.pro != NTT_PRO_BEXT || fio.bx_tab[e] == fio.bx_tab[l]))
+        ++e;
+      fio.tg_l0[k] = (unsigned char)l;
+      fio.tg_n[k] = (unsigned char)(e - l);
+      ++k;
+      l = e;
     }
+    fio.ntg = k;
+    fio.tgroup = r.tgroup;
     ntt_io(fio, false, src_per_job);
   }
   // src_per_job: NTT_PRO_BEXT launches, the mean source limbs read per
@@ -1233,7 +1228,7 @@ struct Context {
     logScale = logScale_;
     h = h_;
     if (L + K > ORION_MAXMOD || L + K > ORION_MAXLIMB) throw std::runtime_error("too many moduli");
-    // the lazy NTT ranges (NTT_INT_CUT keeps forward values in [0, 8q)) and
+    // the lazy NTT ranges (the cut quotient keeps forward values in [0, 8q)) and
     // lt_bsgs's 8-product Barrett (barrett_8q2, bar_k <= 60 for x < 8 q^2)
     // hold only for moduli below 2^61 (ntt_arith.h)
     for (u64 q : m)
@@ -2303,8 +2298,7 @@ struct Context {
       T.sdiags.emplace(kv.first, dst);
     }
     // a zero diagonal in every plan slot an entry does not use, so lt_bsgs can
-    // run its slots without per-slot branches (LT_DENSE; the products with it
-    // add zero)
+    // run its slots without per-slot branches (the products with it add zero)
     {
       if (T.sdiags.empty()) throw std::runtime_error("linear transform has no diagonals loaded");
       const Poly& any = T.sdiags.begin()->second;

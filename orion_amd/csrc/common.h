@@ -40,7 +40,7 @@ struct ModConst {
   // unfolds a_e = (b_e + W b_{N-e}) / 2, with the 1/2 folded into ninv = (2N)^-1.
   // Zero in a Standard ring.
   u64 ciw, ciw_s;
-  // the inverse NTT's last stage with N^-1 folded in (ntt.hip NTT_INV_FOLD):
+  // the inverse NTT's last stage with N^-1 folded in (ntt_arith.h gs_last):
   // X = (x + y) N^-1, Y = (x - y) w1 N^-1, w1 = the stage's twiddle (inv[1])
   u64 wl, wl_s;
   double wl_d;  // centered
@@ -126,7 +126,7 @@ __device__ __forceinline__ u64 shoup_lazy_nq(u64 a, u64 w, u64 ws, u64 nq) {
 
 // the same with the quotient cut: the high word of a0*s0 and the low carries
 // are dropped, so qh <= floor(a*ws/2^64) <= qh + 2 and the result is in
-// [0, 4q) (ntt_arith.h NTT_INT_CUT): 4 v_mad_u64_u32 + 4 v_mul_lo_u32
+// [0, 4q) (ntt_arith.h IntArith::smul): 4 v_mad_u64_u32 + 4 v_mul_lo_u32
 __device__ __forceinline__ u64 shoup_cut_nq(u64 a, u64 w, u64 ws, u64 nq) {
   const u32 a0 = (u32)a, a1 = (u32)(a >> 32), s0 = (u32)ws, s1 = (u32)(ws >> 32);
   const u64 m1 = (u64)a1 * s0;
@@ -720,7 +720,7 @@ __device__ __forceinline__ u64 bext2_apply(const Bext2& c, u64 x0, u64 x1) {
 //            NTT_EPI_SUBSCALE_AUT: the same, element e stored at position aut[e]
 //            NTT_EPI_SUBSCALE_AUT_ACC: ... added to the word at aut[e]
 // ---------------------------------------------------------------------------
-// NTT_PRO_*, NTT_EPI_* and NTT2S_R4: ntt_consts.h
+// NTT_PRO_* and NTT_EPI_*: ntt_consts.h
 __host__ __device__ constexpr bool epi_aut(int epi) { return epi == NTT_EPI_SUBSCALE_AUT || epi == NTT_EPI_SUBSCALE_AUT_ACC; }
 struct NttIO {
   LimbSet dst, src, ex;
@@ -743,7 +743,7 @@ struct NttIO {
   // their inverse columns pass itself, in registers and LDS
   int ifuse;
   LimbSet imid;
-  // ifuse, radix-4, tgroup = G > 1 (ntt2s_ifwd_cols_p): a workgroup of G x 256
+  // ifuse, tgroup = G = 2 (ntt2s_ifwd_cols_p): a workgroup of G x 256
   // threads per (component, image) row, target segment and column tile; the
   // ntg segments (consecutive target limbs that read the same source limbs)
   // start at limb tg_l0[k] and hold tg_n[k] <= G targets
@@ -757,8 +757,8 @@ struct NttIO {
 
 // ---------------------------------------------------------------------------
 // operands of moduli below 2^48 split at bit 24 and kept as (lo 24 bits | hi
-// part << 32) (lt_bsgs's diagonal copies); the partial sums of split products
-// are folded by macs_reduce.
+// part << 32) (lt_bsgs's diagonal copies); the piece products are summed in
+// float64 (MacD below).
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ u64 split24(u64 x) { return (x & 0xffffffull) | ((x >> 24) << 32); }
 // operands of 48..60-bit moduli split at bit 30, kept as (lo 30 bits | hi 30
@@ -786,16 +786,6 @@ __device__ __forceinline__ u64 macw_reduce8(const MacW& a, const ModConst& m) {
   const u64 H = (a.mid >> 34) + (a.hi >> 4) + (L1 < ml) + (L < hl);
   return barrett_8q2(H, L, m);
 }
-struct MacS {
-  u64 lo, mid, hi;
-};
-// x = hi 2^48 + mid 2^24 + lo  (< 128 q^2)  ->  x mod q
-__device__ __forceinline__ u64 macs_reduce(const MacS& a, const ModConst& m) {
-  const u64 L1 = a.lo + (a.mid << 24);
-  const u64 L2 = L1 + (a.hi << 48);
-  const u64 H = (a.mid >> 40) + (a.hi >> 16) + (L1 < a.lo) + (L2 < L1);
-  return barrett_256q2(H, L2, m);
-}
 
 // ---------------------------------------------------------------------------
 // the same split products in float64 (moduli below 2^48): the 24-bit pieces
@@ -820,9 +810,6 @@ __device__ __forceinline__ u64 d53_to_u64(double d) {
   const double l = __builtin_fma(-h, 0x1p32, d);
   return ((u64)(u32)h << 32) | (u32)l;
 }
-#ifndef LT_F64_RED
-#define LT_F64_RED 1
-#endif
 // a representative of x mod q for an exact integer double x (below 2^53, or a
 // reduced value times a power of two as below): x - rint(x RN(1/q)) q.  The
 // estimate x RN(1/q) is within (x/q) 2^-51 of x/q, so the exact remainder is
@@ -832,25 +819,18 @@ __device__ __forceinline__ double f64_rem(double x, double q, double qi) {
   return __builtin_fma(-__builtin_rint(x * qi), q, x);
 }
 __device__ __forceinline__ u64 macd_reduce(const MacD& a, const ModConst& m) {
-  if (LT_F64_RED) {
-    // x = hi 2^48 + mid 2^24 + lo reduced in float64: each piece (< 2^53) to
-    // |r| < 2.5 q, the two high ones scaled by their power of two (exact) and
-    // reduced again (r 2^48 / q < 2^50: the estimate is within 1/2 of the
-    // real quotient, |r| < q), the three summed exactly (< 2^51), reduced to
-    // |s| <= q/2 + 1 and brought to [0, q)
-    const double q = m.qd, qi = m.qinv_d;
-    const double rl = f64_rem(a.lo, q, qi);
-    const double rm = f64_rem(f64_rem(a.mid, q, qi) * 0x1p24, q, qi);
-    const double rh = f64_rem(f64_rem(a.hi, q, qi) * 0x1p48, q, qi);
-    double s = f64_rem((rl + rm) + rh, q, qi);
-    s = s < 0.0 ? s + q : s;
-    return d53_to_u64(s);
-  }
-  MacS s;
-  s.lo = d53_to_u64(a.lo);
-  s.mid = d53_to_u64(a.mid);
-  s.hi = d53_to_u64(a.hi);
-  return macs_reduce(s, m);
+  // x = hi 2^48 + mid 2^24 + lo reduced in float64: each piece (< 2^53) to
+  // |r| < 2.5 q, the two high ones scaled by their power of two (exact) and
+  // reduced again (r 2^48 / q < 2^50: the estimate is within 1/2 of the
+  // real quotient, |r| < q), the three summed exactly (< 2^51), reduced to
+  // |s| <= q/2 + 1 and brought to [0, q)
+  const double q = m.qd, qi = m.qinv_d;
+  const double rl = f64_rem(a.lo, q, qi);
+  const double rm = f64_rem(f64_rem(a.mid, q, qi) * 0x1p24, q, qi);
+  const double rh = f64_rem(f64_rem(a.hi, q, qi) * 0x1p48, q, qi);
+  double s = f64_rem((rl + rm) + rh, q, qi);
+  s = s < 0.0 ? s + q : s;
+  return d53_to_u64(s);
 }
 
 // ---------------------------------------------------------------------------

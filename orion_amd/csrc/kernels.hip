@@ -12,70 +12,6 @@
 #include "ntt2s_rows.h"
 #include "tensor_sum.h"
 
-// timing-only ablation of lt_bsgs (0 in the product): bit 0 skips the giant
-// inner products of moduli below 2^48, bit 1 skips the baby gadget products,
-// bit 2 the giant products of the integer-path (>= 2^48) moduli, bit 3 their
-// baby gadget products, bit 4 replaces the giants' diagonal loads by values
-// formed in registers
-#ifndef LT_ABLATE
-#define LT_ABLATE 0
-#endif
-// 1: ks_mac reduces once per output on moduli below 2^52 instead of once per
-// chunk of 4 digits.  Off: the accumulators live across the digit loop (84 ->
-// 102 VGPRs, 5 -> 4 waves per SIMD) and the LoLA bench measured ks_mac 1.31
-// -> 1.48 ms per step with it (profiles/r03n_ab.txt); LoLA's decompositions
-// have at most 3 digits, so there is one chunk anyway
-#ifndef KS_MAC_ACC
-#define KS_MAC_ACC 0
-#endif
-// ks_mac: digits per load chunk (4 -> 2: 84 -> 62 VGPRs, 5 -> 8 waves per
-// SIMD; ks_mac 104.3 -> 96.6 us per launch, profiles/r03z_ks_mac_chunk_ab.txt)
-#ifndef KS_CH
-#define KS_CH 2
-#endif
-// 1: lt_giant accumulates all giants unreduced on moduli below 2^52
-#ifndef LT_GIANT_ACC
-#define LT_GIANT_ACC 1
-#endif
-#ifndef LT_INT_ACC8
-#define LT_INT_ACC8 1
-#endif
-#ifndef LT_WAVES8
-#define LT_WAVES8 4  // lt_bsgs_kernel8: minimum waves per SIMD (VGPR budget 512 / this)
-#endif
-// 1: lt_bsgs's 48..60-bit limbs multiply 30-bit pieces (split30 diagonals)
-#ifndef LT_INT30
-#define LT_INT30 1
-#endif
-// images per lt_giant thread
-#ifndef LT_GIANT_IB
-#define LT_GIANT_IB 4
-#endif
-#ifndef LT_GIANT_B1
-#define LT_GIANT_B1 1  // 1: one-image launches take lt_giant_kernel<1, ...>
-#endif
-#ifndef LT_GIANT_CH
-#define LT_GIANT_CH 0  // lt_giant digits per load chunk (0: 2 at IB >= 4, else 4)
-#endif
-// 1: lt_bsgs runs every register slot of every giant without branches: the
-// plan points the slots a giant does not use at a zero diagonal, so their
-// products add zero (0: one uniform branch per slot)
-#ifndef LT_DENSE
-#define LT_DENSE 1
-#endif
-// 1: lt_bsgs cuts the baby rotations into 30-bit pieces once, before the
-// integer giant loop (0: per giant)
-#ifndef LT_PRESPLIT
-#define LT_PRESPLIT 1
-#endif
-// images per lt_bsgs workgroup that share one staged copy of the diagonals
-#define LT_IW 4
-// 0 (timing builds only): launches of 4 images and more keep the
-// one-image-per-workgroup mapping
-#ifndef LT_SHARED
-#define LT_SHARED 1
-#endif
-
 namespace {
 
 // the workgroup size of every kernel in this file (launch_bounds and launches:
@@ -83,6 +19,16 @@ namespace {
 // dispatch's implicit arguments (the remainder for a partial last block) with
 // a 16-bit vector load and waits for it before any address is formed
 constexpr int kBlk = 256;
+
+// ks_mac: digits per load chunk (4 -> 2: 84 -> 62 VGPRs, 5 -> 8 waves per
+// SIMD; ks_mac 104.3 -> 96.6 us per launch, profiles/r03z_ks_mac_chunk_ab.txt)
+constexpr int KS_CH = 2;
+// lt_bsgs_kernel8: minimum waves per SIMD (VGPR budget 512 / this); a macro: used inside an attribute
+#define LT_WAVES8 4
+// images per lt_bsgs workgroup that share one staged copy of the diagonals
+constexpr int LT_IW = 4;
+// images per lt_giant thread
+constexpr int LT_GIANT_IB = 4;
 
 // p[i] through a global-address-space pointer: for a pointer read from device
 // memory (a plan's diagonal table) the compiler cannot infer the address
@@ -107,7 +53,7 @@ enum EwOp : int {
   EW_SUBSCALE = 7, // o = (a - b) * s_l
   EW_COPY = 8,     // o = a
   EW_ADDSCALE = 9, // o = o + a * s_l
-  EW_SPLIT24 = 10, // o = split24(a) on limbs below 2^48, split30(a) on limbs up to 2^60 (LT_INT30), else a
+  EW_SPLIT24 = 10, // o = split24(a) on limbs below 2^48, split30(a) on limbs up to 2^60, else a
                    // (lt_bsgs's split-MAC operand forms)
 };
 
@@ -153,7 +99,7 @@ __global__ void __launch_bounds__(256) ew_kernel(LimbSet o, LimbSet a, LimbSet b
     case EW_COPY: z = x; break;
     case EW_SPLIT24:
       z = mc.bar_k <= 48                 ? make_ulonglong2(split24(x.x), split24(x.y))
-          : (LT_INT30 && mc.bar_k <= 60) ? make_ulonglong2(split30(x.x), split30(x.y))
+          : mc.bar_k <= 60 ? make_ulonglong2(split30(x.x), split30(x.y))
                                          : x;
       break;
     case EW_ADDSCALE: {
@@ -557,9 +503,10 @@ __device__ __forceinline__ void ks_mac_body(LimbSet& out, LimbSet& D, LimbSet& o
     __syncthreads();  // fr complete
     fr = frw;
   }
-  // moduli below 2^52 (block-uniform): the digits' products are reduced once
-  // at the end (mac_reduce_small takes up to 128), not once per chunk of 4
-  const bool small = KS_MAC_ACC && mc.bar_k <= 52 && beta <= 120;
+  // one reduction per chunk.  (Once per output on moduli below 2^52 keeps the
+  // accumulators live across the digit loop: 84 -> 102 VGPRs, 5 -> 4 waves per
+  // SIMD, ks_mac 1.31 -> 1.48 ms per LoLA step, profiles/r03n_ab.txt; LoLA's
+  // decompositions have at most 3 digits, so there is one chunk anyway)
   MacAcc s0x, s0y, s1x, s1y;
   mac_zero(s0x), mac_zero(s0y), mac_zero(s1x), mac_zero(s1y);
   if constexpr (pre) {
@@ -613,19 +560,11 @@ __device__ __forceinline__ void ks_mac_body(LimbSet& out, LimbSet& D, LimbSet& o
         mac_add(s1y, d[u].y, ka[u].y);
       }
     }
-    if (!small) {
-      r0.x = add_mod(r0.x, mac_reduce(s0x, mc), q);
-      r0.y = add_mod(r0.y, mac_reduce(s0y, mc), q);
-      r1.x = add_mod(r1.x, mac_reduce(s1x, mc), q);
-      r1.y = add_mod(r1.y, mac_reduce(s1y, mc), q);
-      mac_zero(s0x), mac_zero(s0y), mac_zero(s1x), mac_zero(s1y);
-    }
-  }
-  if (small) {
-    r0.x = add_mod(r0.x, mac_reduce_small(s0x, mc), q);
-    r0.y = add_mod(r0.y, mac_reduce_small(s0y, mc), q);
-    r1.x = add_mod(r1.x, mac_reduce_small(s1x, mc), q);
-    r1.y = add_mod(r1.y, mac_reduce_small(s1y, mc), q);
+    r0.x = add_mod(r0.x, mac_reduce(s0x, mc), q);
+    r0.y = add_mod(r0.y, mac_reduce(s0y, mc), q);
+    r1.x = add_mod(r1.x, mac_reduce(s1x, mc), q);
+    r1.y = add_mod(r1.y, mac_reduce(s1y, mc), q);
+    mac_zero(s0x), mac_zero(s0y), mac_zero(s1x), mac_zero(s1y);
   }
   if constexpr (ROWS) {
     if (l >= G.rows_from) {  // (block-uniform) a P limb: the ModDown INTT's rows pass, here
@@ -854,7 +793,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
   for (int s = 0; s < MB; ++s) {
     x0[s] = x1[s] = 0;
     if (s < Bb.nb && (IW == 1 || active)) {
-      if (Bb.key[s] && !(LT_ABLATE & 2) && !((LT_ABLATE & 8) && mc.bar_k > 48)) {
+      if (Bb.key[s]) {
         const int j = jx[s];
         u64 r0, r1;
         // (a split30 copy of the keys with carry-free MacW products measured
@@ -877,12 +816,8 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
   u64 stg[RW];
   int cur = 0;
   auto fetch = [&](int g) {
-    const unsigned long long mask = P->mask[g] >> Bb.s0;
 #pragma unroll
-    for (int k = 0; k < RW; ++k) {
-      const int s = wv + IW * k;
-      stg[k] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
-    }
+    for (int k = 0; k < RW; ++k) stg[k] = gld(P->pt[g][Bb.s0 + wv + IW * k], po);
   };
   auto put = [&](int buf) {
 #pragma unroll
@@ -921,13 +856,16 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
       xb0[s] = (double)(u32)(x0[s] & 0xffffffull), xa0[s] = (double)(u32)(x0[s] >> 24);
       xb1[s] = (double)(u32)(x1[s] & 0xffffffull), xa1[s] = (double)(u32)(x1[s] >> 24);
     }
-    // the giant loop instantiated with and without accumulation (uniform)
+    // the giant loop instantiated with and without accumulation (uniform).
+    // Every register slot of every giant runs without branches: the plan
+    // points the slots a giant does not use at a zero diagonal, so their
+    // products add zero
     auto giants = [&](auto acc_tag) {
       diag_first();
       for (int g = g0; g < g1; ++g) {
         const bool ACC = ONE ? decltype(acc_tag)::value : adds(g);  // (a layer's entries: per entry, uniform)
         const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
-        const unsigned long long mask = P->mask[g] >> Bb.s0;
+        const u64* const* rows = P->pt[g];  // the giant's diagonals, by slot
         u64 r0 = 0, r1 = 0;
         if (ACC && (IW == 1 || active)) {
           r0 = t0.p[to0];
@@ -936,7 +874,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
         u64 pv[MB];
         if constexpr (IW == 1) {
 #pragma unroll
-          for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+          for (int s = 0; s < MB; ++s) pv[s] = gld(rows[Bb.s0 + s], po);
         } else {
           diag(g, pv);
           if (!active) {
@@ -948,16 +886,14 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
         macd_zero(a0), macd_zero(a1);
 #pragma unroll
         for (int s = 0; s < MB; ++s) {
-          if ((LT_DENSE || ((mask >> s) & 1ull)) && !(LT_ABLATE & 1)) {
-            // the plan's diagonal copies are stored split (EW_SPLIT24): pieces in the two dwords
-            // (signed conversions of the dwords: converting (u32)(pv >> 32) went
-            // through the u64 conversion and left an add of 0.0 * 2^32 behind)
-            u32 w[2];
-            __builtin_memcpy(w, &pv[s], 8);
-            const double pb = (double)(int)w[0], pa = (double)(int)w[1];  // pieces < 2^24
-            macd_add(a0, xb0[s], xa0[s], pb, pa);
-            macd_add(a1, xb1[s], xa1[s], pb, pa);
-          }
+          // the plan's diagonal copies are stored split (EW_SPLIT24): pieces in the two dwords
+          // (signed conversions of the dwords: converting (u32)(pv >> 32) went
+          // through the u64 conversion and left an add of 0.0 * 2^32 behind)
+          u32 w[2];
+          __builtin_memcpy(w, &pv[s], 8);
+          const double pb = (double)(int)w[0], pa = (double)(int)w[1];  // pieces < 2^24
+          macd_add(a0, xb0[s], xa0[s], pb, pa);
+          macd_add(a1, xb1[s], xa1[s], pb, pa);
         }
         const u64 v0 = macd_reduce(a0, mc), v1 = macd_reduce(a1, mc);
         r0 = ACC ? add_mod(r0, v0, mc.q) : v0;
@@ -971,19 +907,17 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     else giants(std::false_type{});
     return;
   }
-  if (LT_INT30 && mc.bar_k <= 60) {
+  if (mc.bar_k <= 60) {
     // 48..60-bit moduli: 30-bit piece products accumulated without carries
     // (MacW, one v_mad_u64_u32 each), one reduction per 8 babies; the plan's
     // diagonal copies are stored split30, and the baby rotations are cut into
     // their pieces once here (the split30 word takes the same two VGPRs), not
     // per giant
-    if (LT_PRESPLIT) {
 #pragma unroll
-      for (int s = 0; s < MB; ++s) x0[s] = split30(x0[s]), x1[s] = split30(x1[s]);
-    }
+    for (int s = 0; s < MB; ++s) x0[s] = split30(x0[s]), x1[s] = split30(x1[s]);
     diag_first();
     for (int g = g0; g < g1; ++g) {
-      const unsigned long long mask = P->mask[g] >> Bb.s0;
+      const u64* const* rows = P->pt[g];  // the giant's diagonals, by slot
       u64 r0 = 0, r1 = 0;
       const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
       if (adds(g) && (IW == 1 || active)) {
@@ -993,7 +927,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
       u64 pv[MB];
       if constexpr (IW == 1) {
 #pragma unroll
-        for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+        for (int s = 0; s < MB; ++s) pv[s] = gld(rows[Bb.s0 + s], po);
       } else {
         diag(g, pv);
         if (!active) {
@@ -1005,16 +939,9 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
       macw_zero(a0), macw_zero(a1);
 #pragma unroll
       for (int s = 0; s < MB; ++s) {
-        if ((LT_DENSE || ((mask >> s) & 1ull)) && !(LT_ABLATE & 4)) {
-          const u32 yb = (u32)pv[s], ya = (u32)(pv[s] >> 32);
-          if (LT_PRESPLIT) {
-            macw_add(a0, (u32)x0[s], (u32)(x0[s] >> 32), yb, ya);
-            macw_add(a1, (u32)x1[s], (u32)(x1[s] >> 32), yb, ya);
-          } else {
-            macw_add(a0, (u32)x0[s] & 0x3fffffffu, (u32)(x0[s] >> 30), yb, ya);
-            macw_add(a1, (u32)x1[s] & 0x3fffffffu, (u32)(x1[s] >> 30), yb, ya);
-          }
-        }
+        const u32 yb = (u32)pv[s], ya = (u32)(pv[s] >> 32);
+        macw_add(a0, (u32)x0[s], (u32)(x0[s] >> 32), yb, ya);
+        macw_add(a1, (u32)x1[s], (u32)(x1[s] >> 32), yb, ya);
         if ((s & 7) == 7) {
           r0 = add_mod(r0, macw_reduce8(a0, mc), mc.q);
           r1 = add_mod(r1, macw_reduce8(a1, mc), mc.q);
@@ -1027,11 +954,15 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     }
     return;
   }
-  // moduli of at most 60 bits: 8 products per reduction (mac_reduce8)
-  const bool acc8 = LT_INT_ACC8 && mc.bar_k <= 60;
+  // moduli of at most 60 bits: 8 products per reduction (mac_reduce8).  (Those
+  // limbs took the 30-bit pieces above, so acc8 is false here; the compiler
+  // does not see that, and without the arm all eight lt_bsgs kernels come out
+  // differently, lt_bsgs_kernel8<false> with 36 B of scratch for 28: it stays
+  // until a change that is timed)
+  const bool acc8 = mc.bar_k <= 60;
   diag_first();
   for (int g = g0; g < g1; ++g) {
-    const unsigned long long mask = P->mask[g] >> Bb.s0;
+    const u64* const* rows = P->pt[g];  // the giant's diagonals, by slot
     u64 r0 = 0, r1 = 0;
     const long long to0 = tgo(t0, g) + ro, to1 = tgo(t1, g) + ro;
     if (adds(g) && (IW == 1 || active)) {
@@ -1043,7 +974,7 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     u64 pv[MB];
     if constexpr (IW == 1) {
 #pragma unroll
-      for (int s = 0; s < MB; ++s) pv[s] = (LT_DENSE || ((mask >> s) & 1ull)) ? ((LT_ABLATE & 16) ? (u64)(po + 977 * s + g) : gld(P->pt[g][Bb.s0 + s], po)) : 0;
+      for (int s = 0; s < MB; ++s) pv[s] = gld(rows[Bb.s0 + s], po);
     } else {
       diag(g, pv);
       if (!active) {
@@ -1055,10 +986,8 @@ __device__ __forceinline__ void lt_bsgs_body(LimbSet& t0, LimbSet& t1, const Lim
     mac_zero(a0), mac_zero(a1);
 #pragma unroll
     for (int s = 0; s < MB; ++s) {
-      if ((LT_DENSE || ((mask >> s) & 1ull)) && !(LT_ABLATE & 4)) {
-        mac_add(a0, pv[s], x0[s]);
-        mac_add(a1, pv[s], x1[s]);
-      }
+      mac_add(a0, pv[s], x0[s]);
+      mac_add(a1, pv[s], x1[s]);
       if (acc8 ? (s & 7) == 7 : (s & 3) == 3) {  // (acc8 is block-uniform)
         r0 = add_mod(r0, acc8 ? mac_reduce8(a0, mc) : mac_reduce(a0, mc), mc.q);
         r1 = add_mod(r1, acc8 ? mac_reduce8(a1, mc) : mac_reduce(a1, mc), mc.q);
@@ -1112,14 +1041,10 @@ lt_bsgs_shared_kernel16(LimbSet t0, LimbSet t1, LimbSet D, LimbSet ct, LtBabies 
 // Each thread takes one coefficient of IB images: the automorphism index, the
 // key words and every pointer step are shared by the IB images, so the key
 // reads from L2 and the scalar address work per product drop IB-fold.
-#ifndef LT_GIANT_WAVES
-#define LT_GIANT_WAVES 0  // timing switch: minimum waves per SIMD for lt_giant (0: the compiler's choice)
-#endif
 template <int IB, bool ROWS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_GIANT_WAVES > 0 ? LT_GIANT_WAVES : 1)))
-lt_giant_kernel(LimbSet acc, LimbSet D, LimbSet own, LimbSet t0, LimbSet z,
+__global__ void __launch_bounds__(256) lt_giant_kernel(LimbSet acc, LimbSet D, LimbSet own, LimbSet t0, LimbSet z,
                                                        LtGiants G, const DeviceTables* __restrict__ tb, int N) {
-  constexpr int CH = LT_GIANT_CH > 0 ? LT_GIANT_CH : (IB >= 4 ? 2 : 4);  // digits per load chunk
+  constexpr int CH = IB >= 4 ? 2 : 4;  // digits per load chunk
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (G.xcd) lt_xcd_decode(bx, by, bz);
   const int b0 = bx * IB;
@@ -1223,7 +1148,7 @@ lt_giant_kernel(LimbSet acc, LimbSet D, LimbSet own, LimbSet t0, LimbSet z,
   // moduli below 2^52: every giant's products and its t0 term go into one
   // unreduced accumulator per image, reduced once per <= 120 products instead
   // of once per giant (the Barrett reduction is ~40 VALU ops per component)
-  if (LT_GIANT_ACC && mc.bar_k <= 52) giants(std::true_type{});  // block-uniform
+  if (mc.bar_k <= 52) giants(std::true_type{});  // block-uniform
   else giants(std::false_type{});
 #pragma unroll
   for (int b = 0; b < IB; ++b) {
@@ -1454,7 +1379,7 @@ int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D,
   // LT_IW images and more: a workgroup is 64 coefficients of LT_IW images and
   // loads their diagonals once (its grid must be exact: the kernel has barriers
   // and no bounds check)
-  const bool shared = LT_SHARED && colB >= LT_IW && N % (256 / LT_IW) == 0;
+  const bool shared = colB >= LT_IW && N % (256 / LT_IW) == 0;
   auto launch = [&](int z0, int nz) {
     if (nz <= 0) return;
     const dim3 g = shared ? dim3((colB + LT_IW - 1) / LT_IW, N / (256 / LT_IW), nz) : dim3(colB, (N + 255) / 256, nz);
@@ -1490,7 +1415,7 @@ int orion_launch_lt_giant(const LimbSet& acc, const LimbSet& D, const LimbSet& o
   if (G.rows_from > 0 && ((G.logN != 15 && G.logN != 16) || N != (1 << G.logN))) return -1;
   // one image (batch 1): the one-image instantiation, whose registers are a
   // quarter of IB = 4's (more waves per SIMD, more loads in flight per CU)
-  const bool one = acc.nbatch == 1 && LT_GIANT_B1;
+  const bool one = acc.nbatch == 1;
   if (one) {
     const dim3 g(1, (N + 255) / 256, acc.nlimb);
     if (G.rows_from > 0)

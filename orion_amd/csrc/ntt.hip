@@ -42,10 +42,6 @@ namespace {
 // Thread t's element e = t + k S (S = N/32) pairs with N - e = (S - t) + (31 - k) S,
 // held at the same offsets of the mirrored thread, so the partner is one more
 // coalesced (descending) load of the same limb, served by L2.
-// 1: the subtract-and-scale epilogue loads its operand one group of 8 rows ahead
-#ifndef NTT_EPI_PF
-#define NTT_EPI_PF 1
-#endif
 
 __device__ __forceinline__ u64 ci_fold(u64 x, u64 y, const ModConst& mc) {
   return sub_mod(x, shoup_mul(y, mc.ciw, mc.ciw_s, mc.q), mc.q);
@@ -95,7 +91,7 @@ __device__ __forceinline__ void ntt_fwd_body(const NttIO& io, int c, int l, int 
   // CT growth is additive (|t| < 2q per stage): from [0, q) the values stay
   // below 31 q over all 15 stages, exact in float64 for q < 2^41, so the
   // round-boundary reductions are only needed for larger float64 moduli
-  const bool lazy = NTT_LAZY && mc.bar_k <= 41;
+  const bool lazy = mc.bar_k <= 41;
   fwd_round<A, LOGN, B0, LOGN - 1, B0>(a, ar, w, t);
   if (!lazy) reduce_all<A>(a, ar);
   xchg<typename A::T, LOGN, B0, B1>(a, lds, t);
@@ -107,29 +103,6 @@ __device__ __forceinline__ void ntt_fwd_body(const NttIO& io, int c, int l, int 
 #pragma unroll
   for (int k = 0; k < 32; ++k) r[k] = ar.final_fwd(a[k]);
   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(row_ptr(io.dst, c, l, b), 0, N * 8, 0x00020000);
-  static_assert(!NTT_FWD_DIRECT || !epi_aut(EPI), "no automorphism epilogue in the direct-store build");
-  if constexpr (NTT_FWD_DIRECT) {  // thread t holds outputs 32 t .. 32 t + 31
-    if constexpr (EPI == NTT_EPI_STORE) {
-#pragma unroll
-      for (int k = 0; k < 32; k += 2) {
-        buf_st2(rd, r[k], r[k + 1], t * 256, k * 8);
-        if ((k & 7) == 6) NTT_FENCE();
-      }
-    } else {
-      const __amdgpu_buffer_rsrc_t rx =
-          __builtin_amdgcn_make_buffer_rsrc(row_ptr(io.ex, c, l, b), 0, N * 8, 0x00020000);
-      const u64 s = io.s[l], ss = io.ss[l];
-#pragma unroll
-      for (int k = 0; k < 32; k += 2) {
-        u64 x, y;
-        buf_ld2(rx, x, y, t * 256, k * 8);
-        buf_st2(rd, shoup_mul(sub_mod(x, r[k], mc.q), s, ss, mc.q), shoup_mul(sub_mod(y, r[k + 1], mc.q), s, ss, mc.q),
-                t * 256, k * 8);
-        if ((k & 7) == 6) NTT_FENCE();
-      }
-    }
-    return;
-  }
   xchg<u64, LOGN, 0, B0>(r, lds, t);
   if constexpr (EPI == NTT_EPI_STORE) {
 #pragma unroll
@@ -172,33 +145,24 @@ __device__ __forceinline__ void ntt_fwd_body(const NttIO& io, int c, int l, int 
   } else {  // NTT_EPI_SUBSCALE: dst = (ex - y) * s_l  (ModDown / rescale tail)
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(row_ptr(io.ex, c, l, b), 0, N * 8, 0x00020000);
     const u64 s = io.s[l], ss = io.ss[l];
-    if constexpr (NTT_EPI_PF) {
-      // ex in groups of 8 rows, the next group's loads issued before the
-      // current group is consumed: one load latency per job instead of four
-      u64 xa[8], xb[8];
+    // ex in groups of 8 rows, the next group's loads issued before the
+    // current group is consumed: one load latency per job instead of four
+    u64 xa[8], xb[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) xa[k] = buf_ld(rx, t * 8, (k << B0) * 8);
+    for (int k = 0; k < 8; ++k) xa[k] = buf_ld(rx, t * 8, (k << B0) * 8);
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (g < 3) {
+    for (int g = 0; g < 4; ++g) {
+      if (g < 3) {
 #pragma unroll
-          for (int k = 0; k < 8; ++k) xb[k] = buf_ld(rx, t * 8, ((8 * (g + 1) + k) << B0) * 8);
-        }
-        NTT_FENCE();
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-          buf_st(rd, shoup_mul(sub_mod(xa[k], r[8 * g + k], mc.q), s, ss, mc.q), t * 8, ((8 * g + k) << B0) * 8);
-        NTT_FENCE();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) xa[k] = xb[k];
+        for (int k = 0; k < 8; ++k) xb[k] = buf_ld(rx, t * 8, ((8 * (g + 1) + k) << B0) * 8);
       }
-    } else {
+      NTT_FENCE();
 #pragma unroll
-      for (int k = 0; k < 32; ++k) {
-        const u64 x = buf_ld(rx, t * 8, (k << B0) * 8);
-        buf_st(rd, shoup_mul(sub_mod(x, r[k], mc.q), s, ss, mc.q), t * 8, (k << B0) * 8);
-        if ((k & 7) == 7) NTT_FENCE();
-      }
+      for (int k = 0; k < 8; ++k)
+        buf_st(rd, shoup_mul(sub_mod(xa[k], r[8 * g + k], mc.q), s, ss, mc.q), t * 8, ((8 * g + k) << B0) * 8);
+      NTT_FENCE();
+#pragma unroll
+      for (int k = 0; k < 8; ++k) xa[k] = xb[k];
     }
   }
 }
@@ -214,27 +178,19 @@ __device__ __forceinline__ void ntt_inv_body(const NttIO& io, int c, int l, int 
   asm volatile("" : "+v"(t));
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(row_ptr(io.src, c, l, b), 0, N * 8, 0x00020000);
   typename A::T a[32];
-  if constexpr (NTT_INV_COAL) {
-    u64 x[32];
 #pragma unroll
-    for (int k = 0; k < 32; ++k) x[k] = buf_ld(rs, t * 8, (k << B0) * 8);
-    xchg<u64, LOGN, B0, 0>(x, lds, t);
-#pragma unroll
-    for (int k = 0; k < 32; ++k) a[k] = ar.from_u64(x[k]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 32; k += 2) {
-      u64 x, y;
-      buf_ld2(rs, x, y, t * 256, k * 8);
-      a[k] = ar.from_u64(x);
-      a[k + 1] = ar.from_u64(y);
-    }
+  for (int k = 0; k < 32; k += 2) {
+    u64 x, y;
+    buf_ld2(rs, x, y, t * 256, k * 8);
+    a[k] = ar.from_u64(x);
+    a[k + 1] = ar.from_u64(y);
   }
+  // no float64 reductions between inverse rounds: a round of GS stages maps
+  // inputs below 8q to outputs below 3q (the sums are reduced every other stage,
+  // mulmod outputs are below 1.5q + ulp), so the bound holds round to round
   inv_round<A, LOGN, 0, 0, B1 - 1>(a, ar, w, t);
-  if (!NTT_INV_NORED) reduce_all<A>(a, ar);
   xchg<typename A::T, LOGN, 0, B1>(a, lds, t);
   inv_round<A, LOGN, B1, B1, B0 - 1>(a, ar, w, t);
-  if (!NTT_INV_NORED) reduce_all<A>(a, ar);
   xchg<typename A::T, LOGN, B1, B0>(a, lds, t);
   inv_round<A, LOGN, B0, B0, LOGN - 1>(a, ar, w, t);
   const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(row_ptr(io.dst, c, l, b), 0, N * 8, 0x00020000);
@@ -249,7 +205,7 @@ __device__ __forceinline__ void ntt_inv_body(const NttIO& io, int c, int l, int 
     u64* const l64 = reinterpret_cast<u64*>(lds);
     u64 r[32];
 #pragma unroll
-    for (int k = 0; k < 32; ++k) r[k] = NTT_INV_FOLD ? ar.final_inv_folded(a[k]) : ar.final_inv(a[k]);
+    for (int k = 0; k < 32; ++k) r[k] = ar.final_inv_folded(a[k]);
 #pragma unroll
     for (int k = 0; k < 16; ++k) l64[k * S + t] = r[k];
     __syncthreads();
@@ -277,42 +233,26 @@ __device__ __forceinline__ void ntt_inv_body(const NttIO& io, int c, int l, int 
   }
 #pragma unroll
   for (int k = 0; k < 32; ++k) {
-    buf_st(rd, NTT_INV_FOLD ? ar.final_inv_folded(a[k]) : ar.final_inv(a[k]), t * 8, (k << B0) * 8);
+    buf_st(rd, ar.final_inv_folded(a[k]), t * 8, (k << B0) * 8);
     if ((k & 3) == 3) NTT_FENCE();
   }
 }
 
 
 // Persistent: a grid of at most one workgroup per CU walks the launch's jobs
-// (job w + k G in round k, or G - 1 - w in odd rounds with NTT_SNAKE; in io.order), so a CU goes from one limb's
-// stores straight to the next limb's loads: no workgroup retire/dispatch
-// bubble between limbs, and the stores drain while the next limb loads and
-// computes.  LDS needs no extra barrier between jobs: every exchange ends
-// with one.
-// The subtract-and-scale epilogue variants keep one job per workgroup: as a
-// loop their extra live values spill (36-41 VGPRs at N = 2^15).
-// 1: the subtract-and-scale (ModDown / rescale tail) variants are persistent
-// too (they no longer spill: 1 VGPR, outside the job loop)
-#ifndef NTT_PERSIST_ALL
-#define NTT_PERSIST_ALL 1
-#endif
-// 1: a persistent workgroup's jobs run in snake order -- job w of every even
-// round, job G - 1 - w of every odd one (G workgroups).  With the integer-path
-// (slower) limbs dispatched first, the workgroups that took the fast float64
-// jobs of a round take the first jobs of the next: a 384-job launch (1.5
-// rounds, one third integer-path) ends after one float64 job more on the
-// float64 workgroups instead of one more after an integer job
-#ifndef NTT_SNAKE
-#define NTT_SNAKE 1
-#endif
-__device__ __forceinline__ int snake_job(int r, int w, int G) {
-  return r * G + ((NTT_SNAKE && (r & 1)) ? G - 1 - w : w);
-}
-
-template <int EPI>
-struct FwdPersist {
-  static constexpr bool value = EPI == NTT_EPI_STORE || NTT_PERSIST_ALL;
-};
+// (in io.order), so a CU goes from one limb's stores straight to the next
+// limb's loads: no workgroup retire/dispatch bubble between limbs, and the
+// stores drain while the next limb loads and computes.  LDS needs no extra
+// barrier between jobs: every exchange ends with one.
+// The subtract-and-scale (ModDown / rescale tail) variants are persistent too
+// (they no longer spill: 1 VGPR, outside the job loop).
+// The jobs run in snake order -- job w of every even round, job G - 1 - w of
+// every odd one (G workgroups).  With the integer-path (slower) limbs
+// dispatched first, the workgroups that took the fast float64 jobs of a round
+// take the first jobs of the next: a 384-job launch (1.5 rounds, one third
+// integer-path) ends after one float64 job more on the float64 workgroups
+// instead of one more after an integer job
+__device__ __forceinline__ int snake_job(int r, int w, int G) { return r * G + ((r & 1) ? G - 1 - w : w); }
 
 template <int LOGN, int PRO, int EPI, bool CI>
 __device__ __forceinline__ void ntt_fwd_job(const NttIO& io, int job, const DeviceTables* __restrict__ tb, u32* lds) {
@@ -333,14 +273,10 @@ __device__ __forceinline__ void ntt_fwd_job(const NttIO& io, int job, const Devi
 template <int LOGN, int PRO, int EPI, bool CI>
 __global__ void __launch_bounds__(NttGeom<LOGN>::T) ntt_fwd_kernel(NttIO io, const DeviceTables* __restrict__ tb) {
   extern __shared__ u32 lds[];
-  if constexpr (FwdPersist<EPI>::value) {
 #pragma nounroll
-    for (int r = 0; r * (int)gridDim.x < io.jobs; ++r) {
-      const int job = snake_job(r, blockIdx.x, gridDim.x);
-      if (job < io.jobs) ntt_fwd_job<LOGN, PRO, EPI, CI>(io, job, tb, lds);
-    }
-  } else {
-    ntt_fwd_job<LOGN, PRO, EPI, CI>(io, blockIdx.x, tb, lds);
+  for (int r = 0; r * (int)gridDim.x < io.jobs; ++r) {
+    const int job = snake_job(r, blockIdx.x, gridDim.x);
+    if (job < io.jobs) ntt_fwd_job<LOGN, PRO, EPI, CI>(io, job, tb, lds);
   }
 }
 
@@ -388,10 +324,10 @@ int launch_ntt_ring(const NttIO& io, const DeviceTables* tb, bool inverse, hipSt
     hipLaunchKernelGGL((ntt_inv_kernel<LOGN, CI>), g, blk, lds, st, io, tb);
     return 0;
   }
-#define FWD(P, E)                                                                                     \
-  if (io.pro == P && io.epi == E) {                                                                   \
-    hipLaunchKernelGGL((ntt_fwd_kernel<LOGN, P, E, CI>), FwdPersist<E>::value ? g : dim3(total), blk, lds, st, io, tb); \
-    return 0;                                                                                         \
+#define FWD(P, E)                                                                \
+  if (io.pro == P && io.epi == E) {                                              \
+    hipLaunchKernelGGL((ntt_fwd_kernel<LOGN, P, E, CI>), g, blk, lds, st, io, tb); \
+    return 0;                                                                    \
   }
   FWD(NTT_PRO_LOAD, NTT_EPI_STORE)
   FWD(NTT_PRO_LOAD, NTT_EPI_SUBSCALE)
@@ -405,15 +341,9 @@ int launch_ntt_ring(const NttIO& io, const DeviceTables* tb, bool inverse, hipSt
   return -1;
 }
 
-// NTT_ONLY15 (register-usage experiments only, never shipped): instantiate
-// the N = 2^15 Standard-ring kernels alone, so one compile takes seconds
 template <int LOGN>
 int launch_ntt(const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t st) {
-#ifdef NTT_ONLY15
-  return io.ci ? -1 : launch_ntt_ring<LOGN, false>(io, tb, inverse, st);
-#else
   return io.ci ? launch_ntt_ring<LOGN, true>(io, tb, inverse, st) : launch_ntt_ring<LOGN, false>(io, tb, inverse, st);
-#endif
 }
 
 template <int LOGN, bool CI>
@@ -429,9 +359,7 @@ void init_lds_ring() {
 template <int LOGN>
 void init_lds() {
   init_lds_ring<LOGN, false>();
-#ifndef NTT_ONLY15
   init_lds_ring<LOGN, true>();
-#endif
 }
 
 }  // namespace
@@ -439,10 +367,8 @@ void init_lds() {
 // host entry: NTT (inverse=false) or INTT with the fused prologue / epilogue of io
 int orion_launch_ntt_io(int logN, const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t st) {
   switch (logN) {
-#ifndef NTT_ONLY15
     case 13: return launch_ntt<13>(io, tb, inverse, st);
     case 14: return launch_ntt<14>(io, tb, inverse, st);
-#endif
     case 15: return launch_ntt<15>(io, tb, inverse, st);
     default: return -1;
   }
@@ -460,10 +386,8 @@ int orion_launch_ntt(int logN, const LimbSet& s, const DeviceTables* tb, bool in
 // allow >64 KiB dynamic LDS for the N = 2^14, 2^15 kernels; size the
 // persistent grid: ORION_NTT_PERSIST workgroups per CU (0 = one per job)
 int orion_ntt_init() {
-#ifndef NTT_ONLY15
   init_lds<13>();
   init_lds<14>();
-#endif
   init_lds<15>();
   const char* e = getenv("ORION_NTT_PERSIST");
   const int per_cu = e ? atoi(e) : 1;

@@ -25,12 +25,6 @@
 
 namespace {
 
-// timing-only ablation (tools/build_ablation.py; 0 in the product): bit 0 =
-// the forward rows pass's per-lane (second-phase) twiddles replaced by one
-// loaded twiddle, bit 1 = the same for the inverse rows pass's first phase
-#ifndef NTT2_TW_ABLATE
-#define NTT2_TW_ABLATE 0
-#endif
 constexpr int A_STRIDE = 18;   // cols pass LDS: [2^R rows][18] u64, conflict-free both ways
 constexpr int B_STRIDE = 272;  // rows pass LDS: [16 rows][256 + 16 pad] u64
 __device__ __forceinline__ int b_lds(int rr, int col) { return rr * B_STRIDE + col + (col >> 4); }
@@ -157,15 +151,12 @@ __device__ __forceinline__ void fwd_rows(const NttIO& io, int c, int l, int b, i
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < 16; ++j) a[j] = from_bits<typename A::T>(lds[b_lds(rr, 16 * jc + j)]);
-  [[maybe_unused]] const typename A::W w_abl = ar.tw(tw, (1 << (LOGN - 4)) + (row << 4), 0);
 #pragma unroll
   for (int d = 3; d >= 0; --d) {
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       if (!((j >> d) & 1))
-        ar.ct(a[j], a[j | (1 << d)],
-              (NTT2_TW_ABLATE & 1) ? w_abl
-                                   : ar.tw(tw, (1 << (LOGN - 1 - d)) + ((row << (7 - d)) | ((16 * jc + j) >> (d + 1))), 0));
+        ar.ct(a[j], a[j | (1 << d)], ar.tw(tw, (1 << (LOGN - 1 - d)) + ((row << (7 - d)) | ((16 * jc + j) >> (d + 1))), 0));
   }
   u64* dst = row_ptr(io.dst, c, l, b) + (row << 8) + 16 * jc;
   if constexpr (EPI == NTT_EPI_STORE) {
@@ -203,15 +194,12 @@ __device__ __forceinline__ void inv_rows(const NttIO& io, int c, int l, int b, i
     a[j] = ar.from_u64(x.x);
     a[j + 1] = ar.from_u64(x.y);
   }
-  [[maybe_unused]] const typename A::W w_abl = ar.tw(tw, (1 << (LOGN - 4)) + (row << 4), 0);
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       if (!((j >> d) & 1))
-        ar.gs(a[j], a[j | (1 << d)],
-              (NTT2_TW_ABLATE & 2) ? w_abl
-                                   : ar.tw(tw, (1 << (LOGN - 1 - d)) + ((row << (7 - d)) | ((16 * jc + j) >> (d + 1))), 0),
+        ar.gs(a[j], a[j | (1 << d)], ar.tw(tw, (1 << (LOGN - 1 - d)) + ((row << (7 - d)) | ((16 * jc + j) >> (d + 1))), 0),
               (d & 1) == 1);
   }
   reduce16<A>(a, ar);
@@ -290,12 +278,8 @@ struct N2 {
   static constexpr int R = LOGN - 8, ATHREADS = 16 << (R - 4), BTILES = 1 << (R - 4);
 };
 
-#ifndef NTT2_COLS_WAVES
-#define NTT2_COLS_WAVES 0  // minimum waves per SIMD for the forward columns pass (0: the compiler's choice)
-#endif
 template <int LOGN, int PRO>
-__global__ void __launch_bounds__(N2<LOGN>::ATHREADS) __attribute__((amdgpu_waves_per_eu(NTT2_COLS_WAVES > 0 ? NTT2_COLS_WAVES : 1)))
-ntt2_fwd_cols(NttIO io, const DeviceTables* __restrict__ tb) {
+__global__ void __launch_bounds__(N2<LOGN>::ATHREADS) ntt2_fwd_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[(1 << N2<LOGN>::R) * A_STRIDE];
   int c, l, b;
   job_of(io, blockIdx.x >> 4, c, l, b);

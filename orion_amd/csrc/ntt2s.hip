@@ -24,39 +24,18 @@ namespace {
 // columns per cols-pass workgroup at N = 2^15, rows per rows-pass workgroup:
 // a launch of J jobs runs J 256/CW (J 2^R/RW) workgroups, and with a few jobs
 // (one image) the time is that of the CUs holding the most workgroups
-#ifndef NTT2S_CW15
-#define NTT2S_CW15 8
-#endif
-#ifndef NTT2S_RW
-#define NTT2S_RW 4
-#endif
-// timing-only ablation (tools/build_ablation.py; 0 in the product): bit 0 =
-// no inverse columns butterflies, bit 1 = no basis-extension / rescale
-// prologue arithmetic in ntt2s_ifwd_cols_p, bit 2 = no forward columns butterflies
-#ifndef NTT2S_ABLATE
-#define NTT2S_ABLATE 0
-#endif
-// 1: ntt2s_ifwd_cols_p fetches its forward twiddles before the INTT half
-#ifndef NTT2S_FWD_PREFETCH
-#define NTT2S_FWD_PREFETCH 0
-#endif
+constexpr int NTT2S_CW15 = 8;
+constexpr int NTT2S_RW = 4;
 template <int LOGN>
 struct S2 {
   static constexpr int R = LOGN - 8;            // row bits: the cols pass transforms 2^R-point columns
   static constexpr int CW = LOGN == 15 ? NTT2S_CW15 : 4;  // columns per cols-pass workgroup
-  static constexpr int H = 1 << (R - 1);         // butterflies per column per stage
-  static constexpr int CT = CW * H;              // cols-pass threads (512)
   static constexpr int CTILES = 256 / CW;        // cols-pass workgroups per limb
   static constexpr int RW = NTT2S_RW;           // rows per rows-pass workgroup
-  static constexpr int RT = RW * 128;            // rows-pass threads (512)
   static constexpr int RTILES = (1 << R) / RW;   // rows-pass workgroups per limb
-  static constexpr int CT4 = CW << (R - 2);      // radix-4 cols-pass threads (256)
-  static constexpr int RT4 = RW * 64;            // radix-4 rows-pass threads (256)
+  static constexpr int CT4 = CW << (R - 2);      // cols-pass threads (256)
+  static constexpr int RT4 = RW * 64;            // rows-pass threads (256)
 };
-
-
-// lower index of butterfly k of a stage on bit `bit` (pairs lo, lo + 2^bit)
-[[maybe_unused]] __device__ __forceinline__ int lo_of(int k, int bit) { return ((k >> bit) << (bit + 1)) | (k & ((1 << bit) - 1)); }
 
 // forward prologue: element e of job (c, l, b)
 template <class A, int PRO>
@@ -80,234 +59,7 @@ __device__ __forceinline__ typename A::T fwd_load(const NttIO& io, int c, int l,
 }
 
 // ---------------------------------------------------------------------------
-// forward cols pass: thread (cl, k) owns butterfly k of column cl in each of
-// the R stages d = LOGN-1 .. 8 (row bit rb = d - 8); twiddle of row group
-// i = lo >> (rb + 1) = k >> rb is w[(N >> (d+1)) + i]
-// ---------------------------------------------------------------------------
-template <class A, int LOGN>
-__device__ __forceinline__ void s_fwd_cols_core(const NttIO& io, int c, int l, int b, int tile,
-                                                typename A::T x, typename A::T y, const A& ar,
-                                                __amdgpu_buffer_rsrc_t tw, u64* lds) {
-  constexpr int N = 1 << LOGN, R = S2<LOGN>::R, CW = S2<LOGN>::CW;
-  const int t = threadIdx.x, cl = t % CW, k = t / CW, col = tile * CW + cl;
-  typename A::W w[R];
-#pragma unroll
-  for (int s = 0; s < R; ++s) {
-    const int rb = R - 1 - s;
-    w[s] = ar.tw(tw, k >> rb, N >> (rb + 9));
-  }
-#pragma unroll
-  for (int s = 0; s < R; ++s) {
-    const int rb = R - 1 - s, lo = lo_of(k, rb);
-    if (s > 0) {
-      x = from_bits<typename A::T>(lds[lo * CW + cl]);
-      y = from_bits<typename A::T>(lds[(lo + (1 << rb)) * CW + cl]);
-    }
-    ar.ct(x, y, w[s]);
-    if (s == 3) x = ar.reduce_round(x), y = ar.reduce_round(y);  // float64: |x| stays below 16q
-    if (s < R - 1) {
-      lds[lo * CW + cl] = to_bits(x);
-      lds[(lo + (1 << rb)) * CW + cl] = to_bits(y);
-      __syncthreads();
-    }
-  }
-  x = ar.reduce_round(x), y = ar.reduce_round(y);
-  u64* mid = row_ptr(io.mid, c, l, b);
-  const int lo = 2 * k;  // the last stage's pair: rows 2k, 2k + 1
-  mid[col + (lo << 8)] = to_bits(x);
-  mid[col + ((lo + 1) << 8)] = to_bits(y);
-}
-template <class A, int LOGN, int PRO>
-__device__ __forceinline__ void s_fwd_cols(const NttIO& io, int c, int l, int b, int tile, const ModConst& mc,
-                                           const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds,
-                                           const DeviceTables* __restrict__ tb) {
-  constexpr int CW = S2<LOGN>::CW, H = S2<LOGN>::H;
-  const int t = threadIdx.x, cl = t % CW, k = t / CW, col = tile * CW + cl;
-  const typename A::T x = fwd_load<A, PRO>(io, c, l, b, col + (k << 8), mc, ar, tb);
-  const typename A::T y = fwd_load<A, PRO>(io, c, l, b, col + ((k + H) << 8), mc, ar, tb);
-  s_fwd_cols_core<A, LOGN>(io, c, l, b, tile, x, y, ar, tw, lds);
-}
-
-// forward rows pass: thread (rr, kk) owns butterfly kk of row rr in each of
-// the stages d = 7 .. 0; twiddle w[(N >> (d+1)) + ((row << (7-d)) | (kk >> d))]
-template <class A, int LOGN, int EPI>
-__device__ __forceinline__ void s_fwd_rows(const NttIO& io, int c, int l, int b, int tile, const ModConst& mc,
-                                           const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds) {
-  constexpr int N = 1 << LOGN;
-  const int t = threadIdx.x, rr = t >> 7, kk = t & 127, row = tile * S2<LOGN>::RW + rr;
-  typename A::W w[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    const int d = 7 - s;
-    w[s] = ar.tw(tw, (row << (7 - d)) | (kk >> d), N >> (d + 1));
-  }
-  const u64* mid = row_ptr(io.mid, c, l, b) + (row << 8);
-  typename A::T x = from_bits<typename A::T>(mid[kk]);
-  typename A::T y = from_bits<typename A::T>(mid[kk + 128]);
-  u64* lr = lds + rr * 256;
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    const int d = 7 - s, lo = lo_of(kk, d);
-    if (s > 0) {
-      x = from_bits<typename A::T>(lr[lo]);
-      y = from_bits<typename A::T>(lr[lo + (1 << d)]);
-    }
-    ar.ct(x, y, w[s]);
-    if (s == 3) x = ar.reduce_round(x), y = ar.reduce_round(y);
-    if (s < 7) {
-      lr[lo] = to_bits(x);
-      lr[lo + (1 << d)] = to_bits(y);
-      __syncthreads();
-    }
-  }
-  // the last stage's pair: columns 2kk, 2kk + 1
-  u64* dst = row_ptr(io.dst, c, l, b) + (row << 8) + 2 * kk;
-  const u64 ox = ar.final_fwd(x), oy = ar.final_fwd(y);
-  if constexpr (EPI == NTT_EPI_STORE) {
-    *(ulonglong2*)dst = make_ulonglong2(ox, oy);
-  } else {  // NTT_EPI_SUBSCALE: dst = (ex - y) * s_l
-    const ulonglong2 e = *(const ulonglong2*)(row_ptr(io.ex, c, l, b) + (row << 8) + 2 * kk);
-    const u64 s = io.s[l], ss = io.ss[l];
-    *(ulonglong2*)dst = make_ulonglong2(shoup_mul(sub_mod(e.x, ox, mc.q), s, ss, mc.q),
-                                        shoup_mul(sub_mod(e.y, oy, mc.q), s, ss, mc.q));
-  }
-}
-
-// inverse rows pass (first): stages d = 0 .. 7, GS; the sum reduced every other stage
-template <class A, int LOGN>
-__device__ __forceinline__ void s_inv_rows(const NttIO& io, int c, int l, int b, int tile, const A& ar,
-                                           __amdgpu_buffer_rsrc_t tw, u64* lds) {
-  constexpr int N = 1 << LOGN;
-  const int t = threadIdx.x, rr = t >> 7, kk = t & 127, row = tile * S2<LOGN>::RW + rr;
-  typename A::W w[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) w[s] = ar.tw(tw, (row << (7 - s)) | (kk >> s), N >> (s + 1));
-  const ulonglong2 v = *(const ulonglong2*)(row_ptr(io.src, c, l, b) + (row << 8) + 2 * kk);
-  typename A::T x = ar.from_u64(v.x), y = ar.from_u64(v.y);
-  u64* lr = lds + rr * 256;
-#pragma unroll
-  for (int d = 0; d < 8; ++d) {
-    const int lo = lo_of(kk, d);
-    if (d > 0) {
-      x = from_bits<typename A::T>(lr[lo]);
-      y = from_bits<typename A::T>(lr[lo + (1 << d)]);
-    }
-    ar.gs(x, y, w[d], (d & 1) == 1);
-    if (d < 7) {
-      lr[lo] = to_bits(x);
-      lr[lo + (1 << d)] = to_bits(y);
-      __syncthreads();
-    }
-  }
-  x = ar.reduce_round(x), y = ar.reduce_round(y);
-  u64* mid = row_ptr(io.mid, c, l, b) + (row << 8);
-  mid[kk] = to_bits(x);  // the last stage's pair: columns kk, kk + 128
-  mid[kk + 128] = to_bits(y);
-}
-
-// inverse cols pass (second): stages d = 8 .. LOGN-1 (row bit rb = d - 8), times N^-1
-template <class A, int LOGN>
-__device__ __forceinline__ void s_inv_cols(const NttIO& io, int c, int l, int b, int tile, const A& ar,
-                                           __amdgpu_buffer_rsrc_t tw, u64* lds) {
-  constexpr int N = 1 << LOGN, R = S2<LOGN>::R, CW = S2<LOGN>::CW, H = S2<LOGN>::H;
-  const int t = threadIdx.x, cl = t % CW, k = t / CW, col = tile * CW + cl;
-  typename A::W w[R];
-#pragma unroll
-  for (int rb = 0; rb < R; ++rb) w[rb] = ar.tw(tw, k >> rb, N >> (rb + 9));
-  const u64* mid = row_ptr(io.mid, c, l, b);
-  typename A::T x = from_bits<typename A::T>(mid[col + ((2 * k) << 8)]);
-  typename A::T y = from_bits<typename A::T>(mid[col + ((2 * k + 1) << 8)]);
-#pragma unroll
-  for (int rb = 0; rb < R; ++rb) {
-    const int lo = lo_of(k, rb);
-    if (rb > 0) {
-      x = from_bits<typename A::T>(lds[lo * CW + cl]);
-      y = from_bits<typename A::T>(lds[(lo + (1 << rb)) * CW + cl]);
-    }
-    ar.gs(x, y, w[rb], (rb & 1) == 1);
-    if (rb < R - 1) {
-      lds[lo * CW + cl] = to_bits(x);
-      lds[(lo + (1 << rb)) * CW + cl] = to_bits(y);
-      __syncthreads();
-    }
-  }
-  u64* dst = row_ptr(io.dst, c, l, b);  // the last stage's pair: rows k, k + H
-  dst[col + (k << 8)] = ar.final_inv(x);
-  dst[col + ((k + H) << 8)] = ar.final_inv(y);
-}
-
-// the inverse's columns pass over one column tile of up to two source limbs
-// (interleaved, one LDS region each), kept in registers: thread (cl, k) ends
-// with rows k and k + H of column col of every source -- exactly the pair its
-// forward columns pass starts from, so the two passes meet without an exchange
-template <class A0, class A1, int LOGN, bool TWO>
-__device__ __forceinline__ void s_inv_cols_src(const u64* m0, const u64* m1, const A0& a0, const A1& a1,
-                                               __amdgpu_buffer_rsrc_t tw0, __amdgpu_buffer_rsrc_t tw1, u64* lds,
-                                               u64 (&xa)[2], u64 (&xb)[2]) {
-  constexpr int N = 1 << LOGN, R = S2<LOGN>::R, CW = S2<LOGN>::CW;
-  const int t = threadIdx.x, cl = t % CW, k = t / CW, col = blockIdx.x % S2<LOGN>::CTILES * CW + cl;
-  typename A0::W w0[R];
-  typename A1::W w1[R];
-#pragma unroll
-  for (int rb = 0; rb < R; ++rb) {
-    w0[rb] = a0.tw(tw0, k >> rb, N >> (rb + 9));
-    if (TWO) w1[rb] = a1.tw(tw1, k >> rb, N >> (rb + 9));
-  }
-  typename A0::T x0 = from_bits<typename A0::T>(m0[col + ((2 * k) << 8)]);
-  typename A0::T y0 = from_bits<typename A0::T>(m0[col + ((2 * k + 1) << 8)]);
-  typename A1::T x1{}, y1{};
-  if (TWO) {
-    x1 = from_bits<typename A1::T>(m1[col + ((2 * k) << 8)]);
-    y1 = from_bits<typename A1::T>(m1[col + ((2 * k + 1) << 8)]);
-  }
-  u64* const l0 = lds;
-  u64* const l1 = lds + (CW << R);
-#pragma unroll
-  for (int rb = 0; rb < R; ++rb) {
-    const int lo = lo_of(k, rb), hi = lo + (1 << rb);
-    if (rb > 0) {
-      x0 = from_bits<typename A0::T>(l0[lo * CW + cl]);
-      y0 = from_bits<typename A0::T>(l0[hi * CW + cl]);
-      if (TWO) {
-        x1 = from_bits<typename A1::T>(l1[lo * CW + cl]);
-        y1 = from_bits<typename A1::T>(l1[hi * CW + cl]);
-      }
-    }
-    a0.gs(x0, y0, w0[rb], (rb & 1) == 1);
-    if (TWO) a1.gs(x1, y1, w1[rb], (rb & 1) == 1);
-    if (rb < R - 1) {
-      l0[lo * CW + cl] = to_bits(x0);
-      l0[hi * CW + cl] = to_bits(y0);
-      if (TWO) {
-        l1[lo * CW + cl] = to_bits(x1);
-        l1[hi * CW + cl] = to_bits(y1);
-      }
-      __syncthreads();
-    }
-  }
-  xa[0] = a0.final_inv(x0), xb[0] = a0.final_inv(y0);
-  if (TWO) xa[1] = a1.final_inv(x1), xb[1] = a1.final_inv(y1);
-}
-
-template <class A0, int LOGN>
-__device__ __forceinline__ void s_inv_cols_src2(const u64* m0, const u64* m1, const A0& a0, int mod1, bool two,
-                                                const DeviceTables* __restrict__ tb, __amdgpu_buffer_rsrc_t tw0,
-                                                u64* lds, u64 (&xa)[2], u64 (&xb)[2]) {
-  if (!two) {
-    s_inv_cols_src<A0, A0, LOGN, false>(m0, m0, a0, a0, tw0, tw0, lds, xa, xb);
-    return;
-  }
-  const ModConst& mc1 = tb->mc[mod1];
-  if (mc1.f64)
-    s_inv_cols_src<A0, F64Arith, LOGN, true>(m0, m1, a0, F64Arith(mc1), tw0, twr_s(tb->inv_d[mod1], 8 << LOGN), lds,
-                                             xa, xb);
-  else
-    s_inv_cols_src<A0, IntArith, LOGN, true>(m0, m1, a0, IntArith(mc1), tw0, twr_s(tb->inv[mod1], 16 << LOGN), lds,
-                                             xa, xb);
-}
-
-// ---------------------------------------------------------------------------
-// radix-4 form (NTT2S_R4): a thread owns 4 elements and runs two stages per
+// radix-4 form: a thread owns 4 elements and runs two stages per
 // LDS exchange (two butterflies per stage), so a pass has half the barriers
 // and exchanges of the one-butterfly form with half the threads.  Step on
 // bits (b, b - 1) (forward) or (b, b + 1) (inverse) over elements
@@ -315,7 +67,7 @@ __device__ __forceinline__ void s_inv_cols_src2(const u64* m0, const u64* m1, co
 //   e2 = e0 + 2^hi_bit, e3 = e2 + 2^lo_bit.
 // An odd stage count ends (forward) or ends (inverse) with one radix-2 stage.
 // A forward columns pass starts on, and an inverse columns pass ends on, the
-// set {j, j + 2^(R-2), j + 2^(R-1), j + 3 2^(R-2)} -- so ntt2s_ifwd_cols needs
+// set {j, j + 2^(R-2), j + 2^(R-1), j + 3 2^(R-2)} -- so ntt2s_ifwd_cols_p needs
 // no exchange between its inverse and forward halves.
 // ---------------------------------------------------------------------------
 // forward columns pass, radix 4: thread (cl, j), j < 2^(R-2)
@@ -358,7 +110,7 @@ __device__ __forceinline__ void s_fwd_cols4_run(const NttIO& io, int c, int l, i
       x[2] = from_bits<typename A::T>(lds[e2 * CW + cl]);
       x[3] = from_bits<typename A::T>(lds[e3 * CW + cl]);
     }
-    if (!(NTT2S_ABLATE & 4)) ct4(ar, x, wa[st], wb[st], wc[st]);
+    ct4(ar, x, wa[st], wb[st], wc[st]);
     if (st == 1)  // after 4 stages (float64: |x| stays below 16q)
       for (int i = 0; i < 4; ++i) x[i] = ar.reduce_round(x[i]);
     if (st < NS - 1 || (R & 1)) {
@@ -372,8 +124,8 @@ __device__ __forceinline__ void s_fwd_cols4_run(const NttIO& io, int c, int l, i
   if (R & 1) {  // the last stage (bit 0): pairs (4j, 4j + 1), (4j + 2, 4j + 3)
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = from_bits<typename A::T>(lds[(4 * j + i) * CW + cl]);
-    if (!(NTT2S_ABLATE & 4)) ar.ct(x[0], x[1], wl[0]);
-    if (!(NTT2S_ABLATE & 4)) ar.ct(x[2], x[3], wl[1]);
+    ar.ct(x[0], x[1], wl[0]);
+    ar.ct(x[2], x[3], wl[1]);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) mid[col + ((4 * j + i) << 8)] = to_bits(ar.reduce_round(x[i]));
@@ -482,39 +234,24 @@ __device__ __forceinline__ void s_inv_rows4(const NttIO& io, int c, int l, int b
   inv_rows4_core<A, LOGN>(x, row, kk, ar, tw, lds + rr * 256, row_ptr(io.mid, c, l, b) + (row << 8));
 }
 
-// inverse columns pass, radix 4 (second), up to two source limbs interleaved
-// (ntt2s_ifwd_cols) or one (ntt2s_inv_cols); ends on the forward's first set
-template <class A0, class A1, int LOGN, bool TWO>
-__device__ __forceinline__ void s_inv_cols4_src(const u64* m0, const u64* m1, const A0& a0, const A1& a1,
-                                                __amdgpu_buffer_rsrc_t tw0, __amdgpu_buffer_rsrc_t tw1, u64* lds,
-                                                typename A0::T (&x)[4], typename A1::T (&y)[4], int t, int tile) {
+// inverse columns pass, radix 4 (second) of one limb's column tile, kept in
+// registers; ends on the forward's first set
+template <class A, int LOGN>
+__device__ __forceinline__ void s_inv_cols4_src(const u64* m, const A& ar, __amdgpu_buffer_rsrc_t tw, u64* lds,
+                                                typename A::T (&x)[4], int t, int tile) {
   constexpr int N = 1 << LOGN, R = S2<LOGN>::R, CW = S2<LOGN>::CW, NS = R / 2, Q = 1 << (R - 2);
   const int cl = t % CW, j = t / CW, col = tile * CW + cl;
-  typename A0::W wa0[NS], wb0[NS], wc0[NS], wl0;
-  typename A1::W wa1[NS], wb1[NS], wc1[NS], wl1;
+  typename A::W wa[NS], wb[NS], wc[NS], wl;
 #pragma unroll
   for (int st = 0; st < NS; ++st) {
     const int lb = 2 * st, g = j >> lb;
-    wa0[st] = a0.tw(tw0, 2 * g, N >> (lb + 9));
-    wb0[st] = a0.tw(tw0, 2 * g + 1, N >> (lb + 9));
-    wc0[st] = a0.tw(tw0, g, N >> (lb + 10));
-    if (TWO) {
-      wa1[st] = a1.tw(tw1, 2 * g, N >> (lb + 9));
-      wb1[st] = a1.tw(tw1, 2 * g + 1, N >> (lb + 9));
-      wc1[st] = a1.tw(tw1, g, N >> (lb + 10));
-    }
+    wa[st] = ar.tw(tw, 2 * g, N >> (lb + 9));
+    wb[st] = ar.tw(tw, 2 * g + 1, N >> (lb + 9));
+    wc[st] = ar.tw(tw, g, N >> (lb + 10));
   }
-  if (R & 1) {  // the last stage (bit R - 1): one twiddle
-    wl0 = a0.tw(tw0, 0, N >> (R + 8));
-    if (TWO) wl1 = a1.tw(tw1, 0, N >> (R + 8));
-  }
+  if (R & 1) wl = ar.tw(tw, 0, N >> (R + 8));  // the last stage (bit R - 1): one twiddle
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    x[i] = from_bits<typename A0::T>(m0[col + ((4 * j + i) << 8)]);
-    if (TWO) y[i] = from_bits<typename A1::T>(m1[col + ((4 * j + i) << 8)]);
-  }
-  u64* const l0 = lds;
-  u64* const l1 = lds + (CW << R);
+  for (int i = 0; i < 4; ++i) x[i] = from_bits<typename A::T>(m[col + ((4 * j + i) << 8)]);
 #pragma unroll
   for (int st = 0; st < NS; ++st) {
     const int lb = 2 * st, hb = lb + 1;
@@ -522,157 +259,35 @@ __device__ __forceinline__ void s_inv_cols4_src(const u64* m0, const u64* m1, co
     const int e[4] = {e0, e1, e2, e3};
     if (st > 0) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        x[i] = from_bits<typename A0::T>(l0[e[i] * CW + cl]);
-        if (TWO) y[i] = from_bits<typename A1::T>(l1[e[i] * CW + cl]);
-      }
+      for (int i = 0; i < 4; ++i) x[i] = from_bits<typename A::T>(lds[e[i] * CW + cl]);
     }
-    if (!(NTT2S_ABLATE & 1)) {
-      gs4(a0, x, wa0[st], wb0[st], wc0[st], false, true);
-      if (TWO) gs4(a1, y, wa1[st], wb1[st], wc1[st], false, true);
-    }
+    gs4(ar, x, wa[st], wb[st], wc[st], false, true);
     if (st < NS - 1 || (R & 1)) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        l0[e[i] * CW + cl] = to_bits(x[i]);
-        if (TWO) l1[e[i] * CW + cl] = to_bits(y[i]);
-      }
+      for (int i = 0; i < 4; ++i) lds[e[i] * CW + cl] = to_bits(x[i]);
       __syncthreads();
     }
   }
   if (R & 1) {  // bit R - 1: pairs (j, j + 2Q), (j + Q, j + 3Q); the sum is not reduced (stage R - 1 even)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      x[i] = from_bits<typename A0::T>(l0[(j + i * Q) * CW + cl]);
-      if (TWO) y[i] = from_bits<typename A1::T>(l1[(j + i * Q) * CW + cl]);
-    }
-    if (!(NTT2S_ABLATE & 1)) a0.gs(x[0], x[2], wl0, ((R - 1) & 1) == 1);
-    if (!(NTT2S_ABLATE & 1)) a0.gs(x[1], x[3], wl0, ((R - 1) & 1) == 1);
-    if (TWO && !(NTT2S_ABLATE & 1)) {
-      a1.gs(y[0], y[2], wl1, ((R - 1) & 1) == 1);
-      a1.gs(y[1], y[3], wl1, ((R - 1) & 1) == 1);
-    }
+    for (int i = 0; i < 4; ++i) x[i] = from_bits<typename A::T>(lds[(j + i * Q) * CW + cl]);
+    ar.gs(x[0], x[2], wl, ((R - 1) & 1) == 1);
+    ar.gs(x[1], x[3], wl, ((R - 1) & 1) == 1);
   }
-}
-
-// the radix-4 inverse columns pass of the sources, to canonical residues:
-// v[s][i] = element i of the thread's set, source s
-template <class A0, int LOGN>
-__device__ __forceinline__ void s_inv_cols4_src2(const u64* m0, const u64* m1, const A0& a0, int mod1, bool two,
-                                                 const DeviceTables* __restrict__ tb, __amdgpu_buffer_rsrc_t tw0,
-                                                 u64* lds, u64 (&v)[2][4], int t, int tile) {
-  typename A0::T x[4];
-  if (!two) {
-    typename A0::T y[4];
-    s_inv_cols4_src<A0, A0, LOGN, false>(m0, m0, a0, a0, tw0, tw0, lds, x, y, t, tile);
-  } else {
-    const ModConst& mc1 = tb->mc[mod1];
-    if (mc1.f64) {
-      const F64Arith a1(mc1);
-      double y[4];
-      s_inv_cols4_src<A0, F64Arith, LOGN, true>(m0, m1, a0, a1, tw0, twr_s(tb->inv_d[mod1], 8 << LOGN), lds, x, y, t,
-                                                  tile);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[1][i] = a1.final_inv(y[i]);
-    } else {
-      const IntArith a1(mc1);
-      u64 y[4];
-      s_inv_cols4_src<A0, IntArith, LOGN, true>(m0, m1, a0, a1, tw0, twr_s(tb->inv[mod1], 16 << LOGN), lds, x, y, t,
-                                                  tile);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[1][i] = a1.final_inv(y[i]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[0][i] = a0.final_inv(x[i]);
 }
 
 // forward columns pass of a launch whose sources skipped the inverse's columns
-// pass (NttIO.ifuse): each workgroup (target job, column tile) finishes the
-// sources' INTT on its tile, forms the prologue (the basis extension, or the
-// rescale prep) from registers, and runs the forward columns stages -- the
-// INTT output never goes to HBM and its second launch disappears
-template <int LOGN, int PRO>
-__global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
-    ntt2s_ifwd_cols(NttIO io, const DeviceTables* __restrict__ tb) {
-  __shared__ u64 lds[2 * (S2<LOGN>::CW << S2<LOGN>::R)];
-  const int job = blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
-  int c, l, b;
-  job_of(io, job, c, l, b);
-  // the sources: limbs sl0 (, sl0 + 1) of src, inverse intermediate in imid
-  int sl0 = 0, ns = 1, ti = 0;
-  const BasisExtTable* __restrict__ T = nullptr;
-  if constexpr (PRO == NTT_PRO_BEXT) {
-    const int kt = arg_byte(io.bx_tab, l);
-    ti = arg_byte(io.bx_t, l);
-    sl0 = arg_byte(io.bx_s0, kt);
-    T = io.bx + kt;
-    ns = T->ns;
-  }
-  [[maybe_unused]] Bext2 bc;  // the extension's constants, before the INTT half (bext2_load)
-  if constexpr (PRO == NTT_PRO_BEXT) bc = bext2_load(T, ti);
-  const int m0 = arg_byte(io.src.mod, sl0), m1 = ns > 1 ? arg_byte(io.src.mod, sl0 + 1) : m0;
-  const u64* p0 = row_ptr(io.imid, c, sl0, b);
-  const u64* p1 = ns > 1 ? row_ptr(io.imid, c, sl0 + 1, b) : p0;
-  const ModConst& mc0 = tb->mc[m0];
-  constexpr int NE = NTT2S_R4 ? 4 : 2;  // elements per thread
-  u64 v[2][NE];
-  if constexpr (NTT2S_R4) {
-    if (mc0.f64)
-      s_inv_cols4_src2<F64Arith, LOGN>(p0, p1, F64Arith(mc0), m1, ns > 1, tb, twr_s(tb->inv_d[m0], 8 << LOGN), lds, v,
-                                       (int)threadIdx.x, tile);
-    else
-      s_inv_cols4_src2<IntArith, LOGN>(p0, p1, IntArith(mc0), m1, ns > 1, tb, twr_s(tb->inv[m0], 16 << LOGN), lds, v,
-                                       (int)threadIdx.x, tile);
-  } else {
-    u64 xa[2] = {0, 0}, xb[2] = {0, 0};
-    if (mc0.f64)
-      s_inv_cols_src2<F64Arith, LOGN>(p0, p1, F64Arith(mc0), m1, ns > 1, tb, twr_s(tb->inv_d[m0], 8 << LOGN), lds, xa,
-                                      xb);
-    else
-      s_inv_cols_src2<IntArith, LOGN>(p0, p1, IntArith(mc0), m1, ns > 1, tb, twr_s(tb->inv[m0], 16 << LOGN), lds, xa,
-                                      xb);
-    v[0][0] = xa[0], v[1][0] = xa[1], v[0][1] = xb[0], v[1][1] = xb[1];
-  }
-  __syncthreads();  // the forward stages reuse the LDS
-  const int mod = arg_byte(io.dst.mod, l);
-  const ModConst mc = tb->mc[mod];
-  u64 o[NE];
-#pragma unroll
-  for (int i = 0; i < NE; ++i) {
-    if constexpr (PRO == NTT_PRO_BEXT) {
-      o[i] = bext2_apply(bc, v[0][i], ns > 1 ? v[1][i] : 0);
-    } else {  // NTT_PRO_RESCALE: ((x + h) mod q_L) mod q_l - (h mod q_l)
-      const u64 qL = tb->mc[io.modL].q, h = qL >> 1;
-      const u64 hm = barrett128(0, h, mc);
-      o[i] = sub_mod(barrett128(0, add_mod(v[0][i], h, qL), mc), hm, mc.q);
-    }
-  }
-  auto fwd = [&](const auto& ar, __amdgpu_buffer_rsrc_t tw) {
-    using A = std::decay_t<decltype(ar)>;
-    if constexpr (NTT2S_R4) {
-      typename A::T x[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) x[i] = ar.from_u64(o[i]);
-      s_fwd_cols4_core<A, LOGN>(io, c, l, b, tile, x, ar, tw, lds, (int)threadIdx.x);
-    } else {
-      s_fwd_cols_core<A, LOGN>(io, c, l, b, tile, ar.from_u64(o[0]), ar.from_u64(o[1]), ar, tw, lds);
-    }
-  };
-  if (mc.f64)
-    fwd(F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN));
-  else
-    fwd(IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN));
-}
-
-// the same with the sources' INTT columns shared by a segment of G targets
-// (NttIO.tgroup = G > 1, radix-4; targets that read the same source limbs): a
-// workgroup of G groups of 256 threads per (row, segment, column tile) runs
-// the sources' INTT columns once -- source s on group s, concurrently -- then
-// every group forms its own target's prologue from the shared values and runs
-// that target's forward columns stages.  The arithmetic is ntt2s_ifwd_cols's
-// (bit-identical); the columns work that kernel redoes for every target is
-// done once per segment, on as many threads per workgroup as targets.
+// pass (NttIO.ifuse): the sources' INTT is finished on the workgroup's column
+// tile, the prologue (the basis extension, or the rescale prep) is formed from
+// registers, and the forward columns stages run -- the INTT output never goes
+// to HBM and its second launch disappears.  The sources' INTT columns are
+// shared by a segment of G targets (NttIO.tgroup = G; targets that read the
+// same source limbs): a workgroup of G groups of 256 threads per (row, segment,
+// column tile) runs the sources' INTT columns once -- source s on group s,
+// concurrently -- then every group forms its own target's prologue from the
+// shared values and runs that target's forward columns stages, on as many
+// threads per workgroup as targets.  (G = 2 ships: four groups measured +8 %,
+// r05r.)
 template <int LOGN>
 __device__ __forceinline__ void idle_inv_cols4_barriers() {  // the barriers of s_inv_cols4_src
   constexpr int R = S2<LOGN>::R, NS = R / 2;
@@ -681,7 +296,6 @@ __device__ __forceinline__ void idle_inv_cols4_barriers() {  // the barriers of 
 }
 template <int LOGN, int PRO, int G>
 __global__ void __launch_bounds__(G * S2<LOGN>::CT4) ntt2s_ifwd_cols_p(NttIO io, const DeviceTables* __restrict__ tb) {
-  static_assert(NTT2S_R4 || LOGN < 0, "radix-4 only");
   constexpr int CT = S2<LOGN>::CT4, REG = S2<LOGN>::CW << S2<LOGN>::R;  // LDS words per group
   __shared__ u64 lds[G * REG + 2 * 4 * CT];
   u64* const sb = lds + G * REG;  // the sources' INTT values, [source][element][thread]
@@ -708,24 +322,6 @@ __global__ void __launch_bounds__(G * S2<LOGN>::CT4) ntt2s_ifwd_cols_p(NttIO io,
   if constexpr (PRO == NTT_PRO_BEXT) bc = bext2_load(T, ti);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
-  // NTT2S_FWD_PREFETCH: the forward stages' twiddles are fetched before the
-  // INTT half, so their latency overlaps it (timing switch)
-  constexpr int NS = S2<LOGN>::R / 2;
-  [[maybe_unused]] ulonglong2 pw[3 * NS + 2];
-  if constexpr (NTT2S_FWD_PREFETCH) {
-    auto pre = [&](const auto& ar, __amdgpu_buffer_rsrc_t tw) {
-      using A = std::decay_t<decltype(ar)>;
-      typename A::W wa[NS], wb[NS], wc[NS], wl[2];
-      s_fwd_cols4_tw<A, LOGN>(ar, tw, t / S2<LOGN>::CW, wa, wb, wc, wl);
-#pragma unroll
-      for (int k = 0; k < NS; ++k) pw[k] = w_raw(wa[k]), pw[NS + k] = w_raw(wb[k]), pw[2 * NS + k] = w_raw(wc[k]);
-      if (S2<LOGN>::R & 1) pw[3 * NS] = w_raw(wl[0]), pw[3 * NS + 1] = w_raw(wl[1]);
-    };
-    if (mc.f64)
-      pre(F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN));
-    else
-      pre(IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN));
-  }
   // phase 1: group s < ns finishes source s's INTT columns on this tile
   if (grp < ns) {
     const int ms = arg_byte(io.src.mod, sl0 + grp);
@@ -733,12 +329,12 @@ __global__ void __launch_bounds__(G * S2<LOGN>::CT4) ntt2s_ifwd_cols_p(NttIO io,
     const ModConst& mcs = tb->mc[ms];
     auto inv = [&](const auto& ar, __amdgpu_buffer_rsrc_t tw) {
       using A = std::decay_t<decltype(ar)>;
-      typename A::T x[4], y[4];
-      s_inv_cols4_src<A, A, LOGN, false>(p, p, ar, ar, tw, tw, lds + grp * REG, x, y, t, tile);
+      typename A::T x[4];
+      s_inv_cols4_src<A, LOGN>(p, ar, tw, lds + grp * REG, x, t, tile);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         u64 xv = ar.final_inv(x[i]);
-        if constexpr (PRO == NTT_PRO_BEXT && !(NTT2S_ABLATE & 2)) {
+        if constexpr (PRO == NTT_PRO_BEXT) {
           if (!bc.centered) {  // (grp wave-uniform: constant table indices on each branch)
             double f;
             xv = __builtin_amdgcn_readfirstlane(grp) == 0 ? bext2_src(bc, 0, xv, f) : bext2_src(bc, 1, xv, f);
@@ -760,9 +356,7 @@ __global__ void __launch_bounds__(G * S2<LOGN>::CT4) ntt2s_ifwd_cols_p(NttIO io,
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const u64 v0 = sb[i * CT + t];
-    if constexpr (NTT2S_ABLATE & 2) {
-      o[i] = v0 + (ns > 1 ? sb[(4 + i) * CT + t] : 0);
-    } else if constexpr (PRO == NTT_PRO_BEXT) {
+    if constexpr (PRO == NTT_PRO_BEXT) {
       const u64 y1 = ns > 1 ? sb[(4 + i) * CT + t] : 0;
       const double f0 = bc.centered ? 0.0 : sf[i * CT + t];
       const double f1 = (bc.centered || ns < 2) ? 0.0 : sf[(4 + i) * CT + t];
@@ -778,16 +372,7 @@ __global__ void __launch_bounds__(G * S2<LOGN>::CT4) ntt2s_ifwd_cols_p(NttIO io,
     typename A::T x[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = ar.from_u64(o[i]);
-    if constexpr (NTT2S_FWD_PREFETCH) {
-      typename A::W wa[NS], wb[NS], wc[NS], wl[2];
-#pragma unroll
-      for (int k = 0; k < NS; ++k)
-        wa[k] = w_of<A>(pw[k]), wb[k] = w_of<A>(pw[NS + k]), wc[k] = w_of<A>(pw[2 * NS + k]);
-      wl[0] = w_of<A>(pw[3 * NS]), wl[1] = w_of<A>(pw[3 * NS + 1]);
-      s_fwd_cols4_run<A, LOGN>(io, c, l, b, tile, x, ar, wa, wb, wc, wl, lds + grp * REG, t);
-    } else {
-      s_fwd_cols4_core<A, LOGN>(io, c, l, b, tile, x, ar, tw, lds + grp * REG, t);
-    }
+    s_fwd_cols4_core<A, LOGN>(io, c, l, b, tile, x, ar, tw, lds + grp * REG, t);
   };
   if (mc.f64)
     fwd(F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN));
@@ -799,7 +384,7 @@ __global__ void __launch_bounds__(G * S2<LOGN>::CT4) ntt2s_ifwd_cols_p(NttIO io,
 // kernels: blockIdx.x = job * tiles + tile
 // ---------------------------------------------------------------------------
 template <int LOGN, int PRO>
-__global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
+__global__ void __launch_bounds__(S2<LOGN>::CT4)
     ntt2s_fwd_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::CW << S2<LOGN>::R];
   const int job = blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
@@ -807,21 +392,14 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
-  if constexpr (NTT2S_R4) {
-    if (mc.f64)
-      s_fwd_cols4<F64Arith, LOGN, PRO>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds,
-                                       tb);
-    else
-      s_fwd_cols4<IntArith, LOGN, PRO>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds,
-                                       tb);
-  } else if (mc.f64)
-    s_fwd_cols<F64Arith, LOGN, PRO>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds, tb);
+  if (mc.f64)
+    s_fwd_cols4<F64Arith, LOGN, PRO>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds, tb);
   else
-    s_fwd_cols<IntArith, LOGN, PRO>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds, tb);
+    s_fwd_cols4<IntArith, LOGN, PRO>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds, tb);
 }
 
 template <int LOGN, int EPI>
-__global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT)
+__global__ void __launch_bounds__(S2<LOGN>::RT4)
     ntt2s_fwd_rows(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::RW * 256];
   const int job = blockIdx.x / S2<LOGN>::RTILES, tile = blockIdx.x % S2<LOGN>::RTILES;
@@ -829,20 +407,14 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT)
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
-  static_assert(NTT2S_R4 || !epi_aut(EPI), "the automorphism epilogue is radix-4 only");
-  if constexpr (NTT2S_R4) {
-    if (mc.f64)
-      s_fwd_rows4<F64Arith, LOGN, EPI>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds);
-    else
-      s_fwd_rows4<IntArith, LOGN, EPI>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds);
-  } else if (mc.f64)
-    s_fwd_rows<F64Arith, LOGN, EPI>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds);
+  if (mc.f64)
+    s_fwd_rows4<F64Arith, LOGN, EPI>(io, c, l, b, tile, mc, F64Arith(mc), twr_s(tb->fwd_d[mod], 8 << LOGN), lds);
   else
-    s_fwd_rows<IntArith, LOGN, EPI>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds);
+    s_fwd_rows4<IntArith, LOGN, EPI>(io, c, l, b, tile, mc, IntArith(mc), twr_s(tb->fwd[mod], 16 << LOGN), lds);
 }
 
 template <int LOGN>
-__global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT)
+__global__ void __launch_bounds__(S2<LOGN>::RT4)
     ntt2s_inv_rows(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::RW * 256];
   const int job = blockIdx.x / S2<LOGN>::RTILES, tile = blockIdx.x % S2<LOGN>::RTILES;
@@ -850,19 +422,14 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT)
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
-  if constexpr (NTT2S_R4) {
-    if (mc.f64)
-      s_inv_rows4<F64Arith, LOGN>(io, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
-    else
-      s_inv_rows4<IntArith, LOGN>(io, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
-  } else if (mc.f64)
-    s_inv_rows<F64Arith, LOGN>(io, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
+  if (mc.f64)
+    s_inv_rows4<F64Arith, LOGN>(io, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
   else
-    s_inv_rows<IntArith, LOGN>(io, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
+    s_inv_rows4<IntArith, LOGN>(io, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
 }
 
 template <int LOGN>
-__global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
+__global__ void __launch_bounds__(S2<LOGN>::CT4)
     ntt2s_inv_cols(NttIO io, const DeviceTables* __restrict__ tb) {
   __shared__ u64 lds[S2<LOGN>::CW << S2<LOGN>::R];
   const int job = blockIdx.x / S2<LOGN>::CTILES, tile = blockIdx.x % S2<LOGN>::CTILES;
@@ -870,26 +437,20 @@ __global__ void __launch_bounds__(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT)
   job_of(io, job, c, l, b);
   const int mod = arg_byte(io.dst.mod, l);
   const ModConst mc = tb->mc[mod];
-  if constexpr (NTT2S_R4) {
-    auto inv = [&](const auto& ar, __amdgpu_buffer_rsrc_t tw) {
-      using A = std::decay_t<decltype(ar)>;
-      constexpr int CW = S2<LOGN>::CW, Q = 1 << (S2<LOGN>::R - 2);
-      const int t = threadIdx.x, cl = t % CW, j = t / CW, col = tile * CW + cl;
-      typename A::T x[4], y[4];
-      const u64* m = row_ptr(io.mid, c, l, b);
-      s_inv_cols4_src<A, A, LOGN, false>(m, m, ar, ar, tw, tw, lds, x, y, t, tile);
-      u64* dst = row_ptr(io.dst, c, l, b);
+  auto inv = [&](const auto& ar, __amdgpu_buffer_rsrc_t tw) {
+    using A = std::decay_t<decltype(ar)>;
+    constexpr int CW = S2<LOGN>::CW, Q = 1 << (S2<LOGN>::R - 2);
+    const int t = threadIdx.x, cl = t % CW, j = t / CW, col = tile * CW + cl;
+    typename A::T x[4];
+    s_inv_cols4_src<A, LOGN>(row_ptr(io.mid, c, l, b), ar, tw, lds, x, t, tile);
+    u64* dst = row_ptr(io.dst, c, l, b);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dst[col + ((j + i * Q) << 8)] = ar.final_inv(x[i]);
-    };
-    if (mc.f64)
-      inv(F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN));
-    else
-      inv(IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN));
-  } else if (mc.f64)
-    s_inv_cols<F64Arith, LOGN>(io, c, l, b, tile, F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN), lds);
+    for (int i = 0; i < 4; ++i) dst[col + ((j + i * Q) << 8)] = ar.final_inv(x[i]);
+  };
+  if (mc.f64)
+    inv(F64Arith(mc), twr_s(tb->inv_d[mod], 8 << LOGN));
   else
-    s_inv_cols<IntArith, LOGN>(io, c, l, b, tile, IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN), lds);
+    inv(IntArith(mc), twr_s(tb->inv[mod], 16 << LOGN));
 }
 
 template <int LOGN>
@@ -897,8 +458,7 @@ int launch2s(const NttIO& io, const DeviceTables* tb, bool inverse, bool rows_on
   const int total = io.dst.ncomp * io.dst.nlimb * io.dst.nbatch;
   if (total == 0) return 0;
   if (io.jobs != total || io.ci) return -1;
-  const dim3 ga(total * S2<LOGN>::CTILES), ba(NTT2S_R4 ? S2<LOGN>::CT4 : S2<LOGN>::CT), gb(total * S2<LOGN>::RTILES),
-      bb(NTT2S_R4 ? S2<LOGN>::RT4 : S2<LOGN>::RT);
+  const dim3 ga(total * S2<LOGN>::CTILES), ba(S2<LOGN>::CT4), gb(total * S2<LOGN>::RTILES), bb(S2<LOGN>::RT4);
   if (inverse) {
     if (io.pro != NTT_PRO_LOAD || io.epi != NTT_EPI_STORE) return -1;
     hipLaunchKernelGGL(ntt2s_inv_rows<LOGN>, gb, bb, 0, st, io, tb);
@@ -907,36 +467,13 @@ int launch2s(const NttIO& io, const DeviceTables* tb, bool inverse, bool rows_on
     if (!rows_only) hipLaunchKernelGGL(ntt2s_inv_cols<LOGN>, ga, ba, 0, st, io, tb);
     return 0;
   }
-  if (io.ifuse && io.tgroup > 1) {
-    if (!io.imid.p || io.ntg < 1) return -1;
-    const dim3 gg(io.dst.ncomp * io.dst.nbatch * io.ntg * S2<LOGN>::CTILES);
-    if constexpr (NTT2S_R4) {
-      const bool bx = io.pro == NTT_PRO_BEXT;
-      if (!bx && io.pro != NTT_PRO_RESCALE) return -1;
-      if (io.tgroup == 2) {
-        const dim3 bg(2 * S2<LOGN>::CT4);
-        if (bx)
-          hipLaunchKernelGGL((ntt2s_ifwd_cols_p<LOGN, NTT_PRO_BEXT, 2>), gg, bg, 0, st, io, tb);
-        else
-          hipLaunchKernelGGL((ntt2s_ifwd_cols_p<LOGN, NTT_PRO_RESCALE, 2>), gg, bg, 0, st, io, tb);
-      } else if (io.tgroup == 4) {
-        const dim3 bg(4 * S2<LOGN>::CT4);
-        if (bx)
-          hipLaunchKernelGGL((ntt2s_ifwd_cols_p<LOGN, NTT_PRO_BEXT, 4>), gg, bg, 0, st, io, tb);
-        else
-          hipLaunchKernelGGL((ntt2s_ifwd_cols_p<LOGN, NTT_PRO_RESCALE, 4>), gg, bg, 0, st, io, tb);
-      } else {
-        return -1;
-      }
-    } else {
-      return -1;
-    }
-  } else if (io.ifuse) {
-    if (!io.imid.p) return -1;
+  if (io.ifuse) {  // the sources' INTT columns shared by pairs of targets
+    if (io.tgroup != 2 || !io.imid.p || io.ntg < 1) return -1;
+    const dim3 gg(io.dst.ncomp * io.dst.nbatch * io.ntg * S2<LOGN>::CTILES), bg(2 * S2<LOGN>::CT4);
     if (io.pro == NTT_PRO_BEXT)
-      hipLaunchKernelGGL((ntt2s_ifwd_cols<LOGN, NTT_PRO_BEXT>), ga, ba, 0, st, io, tb);
+      hipLaunchKernelGGL((ntt2s_ifwd_cols_p<LOGN, NTT_PRO_BEXT, 2>), gg, bg, 0, st, io, tb);
     else if (io.pro == NTT_PRO_RESCALE)
-      hipLaunchKernelGGL((ntt2s_ifwd_cols<LOGN, NTT_PRO_RESCALE>), ga, ba, 0, st, io, tb);
+      hipLaunchKernelGGL((ntt2s_ifwd_cols_p<LOGN, NTT_PRO_RESCALE, 2>), gg, bg, 0, st, io, tb);
     else
       return -1;
   } else if (io.pro == NTT_PRO_LOAD)
@@ -955,10 +492,10 @@ int launch2s(const NttIO& io, const DeviceTables* tb, bool inverse, bool rows_on
     hipLaunchKernelGGL((ntt2s_fwd_rows<LOGN, NTT_EPI_STORE>), gb, bb, 0, st, io, tb);
   else if (io.epi == NTT_EPI_SUBSCALE)
     hipLaunchKernelGGL((ntt2s_fwd_rows<LOGN, NTT_EPI_SUBSCALE>), gb, bb, 0, st, io, tb);
-  else if (io.epi == NTT_EPI_SUBSCALE_AUT && NTT2S_R4 && io.aut)
-    hipLaunchKernelGGL((ntt2s_fwd_rows<LOGN, NTT2S_R4 ? NTT_EPI_SUBSCALE_AUT : NTT_EPI_SUBSCALE>), gb, bb, 0, st, io, tb);
-  else if (io.epi == NTT_EPI_SUBSCALE_AUT_ACC && NTT2S_R4 && io.aut)
-    hipLaunchKernelGGL((ntt2s_fwd_rows<LOGN, NTT2S_R4 ? NTT_EPI_SUBSCALE_AUT_ACC : NTT_EPI_SUBSCALE>), gb, bb, 0, st, io, tb);
+  else if (io.epi == NTT_EPI_SUBSCALE_AUT && io.aut)
+    hipLaunchKernelGGL((ntt2s_fwd_rows<LOGN, NTT_EPI_SUBSCALE_AUT>), gb, bb, 0, st, io, tb);
+  else if (io.epi == NTT_EPI_SUBSCALE_AUT_ACC && io.aut)
+    hipLaunchKernelGGL((ntt2s_fwd_rows<LOGN, NTT_EPI_SUBSCALE_AUT_ACC>), gb, bb, 0, st, io, tb);
   else
     return -1;
   return 0;

@@ -11,7 +11,3 @@ enum { NTT_PRO_LOAD = 0, NTT_PRO_RESCALE = 2, NTT_PRO_BEXT = 3 };
 // NTT_EPI_SUBSCALE_AUT_ACC: the same, added to the word already at aut[e] (a
 // rotation whose result is added to its own input, x += sigma_g(x))
 enum { NTT_EPI_STORE = 0, NTT_EPI_SUBSCALE = 1, NTT_EPI_SUBSCALE_AUT = 2, NTT_EPI_SUBSCALE_AUT_ACC = 3 };
-// 1: the latency kernels (ntt2s.hip) run in radix-4 form
-#ifndef NTT2S_R4
-#define NTT2S_R4 1
-#endif

@@ -6,51 +6,6 @@
 
 #include "ntt_arith.h"
 
-// timing-only ablation builds (tools/build_ablation.py + tools/ab.sh); 0 in the product:
-// bit 0 skips the butterfly rounds, bit 1 skips the LDS exchanges
-#ifndef NTT_ABLATE
-#define NTT_ABLATE 0
-#endif
-// timing switch: NTT_LAZY skips the forward round
-// reductions for small float64 moduli
-#ifndef NTT_LAZY
-#define NTT_LAZY 1
-#endif
-// timing switch: 1 = the forward kernel stores its last round directly (each
-// thread's 32 consecutive outputs as 16-B stores) instead of exchanging back
-// to the strided layout first
-#ifndef NTT_FWD_DIRECT
-#define NTT_FWD_DIRECT 0
-#endif
-// timing switch: 1 = the inverse kernel loads coalesced (element t + 1024 k)
-// and exchanges to the consecutive layout, instead of 16-B strided loads
-#ifndef NTT_INV_COAL
-#define NTT_INV_COAL 0
-#endif
-// scheduling windows: a sched_barrier after every NTT_FENCE_FWD (forward) /
-// NTT_FENCE_INV (inverse) butterflies bounds the live registers to <= 128
-#ifndef NTT_FENCE_FWD
-#define NTT_FENCE_FWD 4
-#endif
-#ifndef NTT_FENCE_INV
-#define NTT_FENCE_INV 2
-#endif
-// 1: the inverse's last stage multiplies by N^-1 (X) and w1 N^-1 (Y) instead
-// of a separate N^-1 pass over every output (ntt.hip final_inv_folded)
-#ifndef NTT_INV_FOLD
-#define NTT_INV_FOLD 1
-#endif
-// 1: no float64 reductions between inverse rounds: a round of GS stages maps
-// inputs below 8q to outputs below 3q (the sums are reduced every other stage,
-// mulmod outputs are below 1.5q + ulp), so the bound holds round to round
-#ifndef NTT_INV_NORED
-#define NTT_INV_NORED 1
-#endif
-// 1: butterflies scheduled in pairs (see run_stage)
-#ifndef NTT_PAIR
-#define NTT_PAIR 0
-#endif
-
 namespace {
 
 template <int LOGN>
@@ -78,7 +33,6 @@ __host__ __device__ constexpr int lds_off(int k) {
 // data's own 64.
 template <class T, int BOLD, int BNEW>
 __device__ __forceinline__ void exchange(T (&a)[32], u32* lds, int t) {
-  if (NTT_ABLATE & 2) return;
   u32 lo[32], hi[32];
   u32* const wr = lds + lds_base<BOLD>(t);
   u32* const rd = lds + lds_base<BNEW>(t);
@@ -113,9 +67,11 @@ __device__ __forceinline__ void xchg(T (&a)[32], u32* lds, int t) {
 // 2^(4-dk) distinct twiddles (dk = stage bit - window base B).  Twiddles are
 // software-prefetched TW_PF groups ahead through a compile-time ring, so the
 // L2 latency of a per-thread twiddle load is hidden behind earlier butterflies.
-#ifndef TW_PF
-#define TW_PF 4
-#endif
+constexpr int TW_PF = 4;
+// scheduling windows: a sched_barrier after every NTT_FENCE_FWD (forward) /
+// NTT_FENCE_INV (inverse) butterflies bounds the live registers to <= 128
+constexpr int NTT_FENCE_FWD = 4;
+constexpr int NTT_FENCE_INV = 2;
 template <int B, int DFIRST, int DLAST>
 struct RoundPlan {
   static constexpr int DIR = DLAST >= DFIRST ? 1 : -1;
@@ -156,7 +112,7 @@ template <class A, int LOGN, int B, class Plan, int S, bool FWD, class TS>
 __device__ __forceinline__ void run_stage(typename A::T (&a)[32], typename A::W (&ring)[TW_PF], const A& ar,
                                           const TS& ts, int thigh) {
   constexpr int d = Plan::d_of(S), dk = d - B;
-  typename A::W W, Wp;
+  typename A::W W;
 #pragma unroll
   for (int pr = 0; pr < 16; ++pr) {
     const int khi = pr >> dk, klo = pr & ((1 << dk) - 1);
@@ -175,34 +131,14 @@ __device__ __forceinline__ void run_stage(typename A::T (&a)[32], typename A::W 
     }
     const int k0 = (khi << (dk + 1)) | klo;
     const int k1 = k0 | (1 << dk);
-    if constexpr (NTT_PAIR) {
-      // two butterflies per scheduling region: the pins sit in front of the
-      // pair, so the scheduler can interleave the two independent chains
-      // (one butterfly is a dependent chain of 8 FP64 or ~30 integer ops)
-      if ((pr & 1) == 0) {
-        Wp = W;
-        continue;
-      }
-      const int pe = pr - 1, ke = ((pe >> dk) << (dk + 1)) | (pe & ((1 << dk) - 1)), ke1 = ke | (1 << dk);
-      PIN(a[ke], a[ke1]);
-      PIN(a[k0], a[k1]);
-      if constexpr (FWD) {
-        ar.ct(a[ke], a[ke1], Wp);
-        ar.ct(a[k0], a[k1], W);
-        if ((pr & (NTT_FENCE_FWD - 1)) == NTT_FENCE_FWD - 1) NTT_FENCE();
-      } else {
-        ar.gs(a[ke], a[ke1], Wp, (S & 1) == 1);
-        ar.gs(a[k0], a[k1], W, (S & 1) == 1);
-        if ((pr & (NTT_FENCE_INV - 1)) == NTT_FENCE_INV - 1 || NTT_FENCE_INV < 2) NTT_FENCE();
-      }
-      continue;
-    }
     PIN(a[k0], a[k1]);
     if constexpr (FWD) {
       ar.ct(a[k0], a[k1], W);
       if ((pr & (NTT_FENCE_FWD - 1)) == NTT_FENCE_FWD - 1) NTT_FENCE();
     } else {
-      if constexpr (NTT_INV_FOLD && d == LOGN - 1)
+      // the last stage multiplies by N^-1 (X) and w1 N^-1 (Y) instead of a
+      // separate N^-1 pass over every output (ntt.hip final_inv_folded)
+      if constexpr (d == LOGN - 1)
         ar.gs_last(a[k0], a[k1]);
       else
         ar.gs(a[k0], a[k1], W, (S & 1) == 1);
@@ -223,7 +159,6 @@ __device__ __forceinline__ void run_stages(typename A::T (&a)[32], typename A::W
 // one round with twiddles from source ts
 template <class A, int LOGN, int B, int DFIRST, int DLAST, bool FWD, class TS>
 __device__ __forceinline__ void do_round_ts(typename A::T (&a)[32], const A& ar, const TS& ts, int t) {
-  if (NTT_ABLATE & 1) return;
   typedef RoundPlan<B, DFIRST, DLAST> Plan;
   const int thigh = t >> B;
   typename A::W ring[TW_PF];

@@ -8,15 +8,11 @@
 #include <cstdlib>
 #include "ntt_consts.h"
 
-#ifndef ORION_NTT_DEFAULT_IMPL
-#define ORION_NTT_DEFAULT_IMPL 1
-#endif
-
 // the launch-path switches, read once per Context (every pipeline context
 // reads the environment at its creation)
 struct NttTuning {
   // 1: one limb per workgroup (ntt.hip); 2: two-pass N = 2^15 kernels (ntt2.hip)
-  int ntt_impl = ORION_NTT_DEFAULT_IMPL;
+  int ntt_impl = 1;
   // N = 2^15 launches with fewer limb-transforms than this use the two-pass
   // kernels: one limb per CU leaves most of the 256 CUs idle there (8 jobs:
   // 15 vs 37 us; 64 jobs: 32 vs 40 us, float64 path).  Batched launches
@@ -51,19 +47,14 @@ struct NttTuning {
   // follows (ModUp and ModDown sources, the rescale's last limb) runs its rows
   // pass alone when both launches take the latency kernels (ntt2s.hip); the
   // forward launch finishes the INTT's columns pass on its own column tile
-  // (ntt2s_ifwd_cols), so the INTT output never goes to HBM and its second
+  // (ntt2s_ifwd_cols_p), so the INTT output never goes to HBM and its second
   // launch disappears
   int ntt_ifuse = 1;
   // ... as long as the sources' columns pass is not redone too often: every
-  // target workgroup redoes it for its own sources, (targets x sources per
+  // pair of targets redoes it for its own sources, (targets x sources per
   // target) / source limbs times the INTT's own columns work (ResNet's
   // N = 2^16 ModDowns onto 20-30 Q limbs measured slower fused)
   double ntt_ifuse_maxr = 8.0;
-  // 2 or 4: the fused forward runs a workgroup of that many 256-thread groups
-  // per segment of targets sharing their sources, which finishes the sources'
-  // INTT columns once for the segment (ntt2s_ifwd_cols_p); 1: one target per
-  // workgroup, the sources' columns redone for each (ntt2s_ifwd_cols)
-  int ntt_ifuse_p = 2;
   // 1: a rotation's NTT-domain automorphism is applied in the ModDown's final
   // NTT store (NTT_EPI_SUBSCALE_AUT) where the kernel supports it
   int ntt_aut_fuse = 1;
@@ -94,7 +85,6 @@ struct NttTuning {
     geti(getenv("ORION_BEXT_FUSE_BELOW"), t.bext_fuse_below);
     geti(getenv("ORION_NTT_IFUSE"), t.ntt_ifuse);
     getd(getenv("ORION_NTT_IFUSE_MAXR"), t.ntt_ifuse_maxr);
-    geti(getenv("ORION_NTT_IFUSE_P"), t.ntt_ifuse_p);
     geti(getenv("ORION_NTT_AUT_FUSE"), t.ntt_aut_fuse);
     geti(getenv("ORION_MODUP_MERGE"), t.modup_merge);
     geti(getenv("ORION_MAC_ROWS"), t.mac_rows);
@@ -111,7 +101,6 @@ struct NttEnv {
   bool ci = false;   // ConjugateInvariant ring
   int K = 0;         // P primes
   int n_cu = 0;      // compute units
-  bool r4 = NTT2S_R4 != 0;  // the latency kernels are built in radix-4 form
   int max_limb = 0, max_src = 0, max_group = 0;  // ORION_MAXLIMB, ORION_MAXSRC, ORION_MAXGROUP (common.h)
 };
 
@@ -161,14 +150,14 @@ inline bool scatter_epilogue(const NttEnv& e, const NttTuning& t, int jobs, int 
   if (e.ci) return false;
   const NttFamily f = ntt_family(e, t, jobs, false, pro, NTT_EPI_SUBSCALE_AUT, false);
   if (f == OnePass) return e.logN <= 15 && pro == NTT_PRO_LOAD;
-  return jobs <= t.ntt2s_below && e.r4;
+  return jobs <= t.ntt2s_below;
 }
 
 // an INTT (load, store) followed by the forward NTT whose BEXT / RESCALE
 // prologue reads only the INTT's output (Context::intt_then_fwd)
 struct InvFwdRoute {
   bool ifuse = false;        // the INTT's rows pass alone, its columns pass inside the forward's latency kernels
-  int tgroup = 0;            // ifuse: targets per workgroup sharing their sources' columns pass (0: one each)
+  int tgroup = 0;            // ifuse: 2, the targets per workgroup sharing their sources' columns pass
   bool rows_stored = false;  // ifuse: the producer's kernel already stored the rows pass' intermediate
 };
 // src_limbs -> dst_limbs limbs over nimg = components x images; ns_max: the
@@ -180,7 +169,7 @@ inline InvFwdRoute inv_fwd_route(const NttEnv& e, const NttTuning& t, int nimg, 
   r.ifuse = t.ntt_ifuse && !e.ci && redo <= t.ntt_ifuse_maxr && (pro == NTT_PRO_BEXT || pro == NTT_PRO_RESCALE) &&
             ntt_family(e, t, nimg * src_limbs, true, NTT_PRO_LOAD, NTT_EPI_STORE, false) == Latency &&
             ntt_family(e, t, nimg * dst_limbs, false, pro, epi, inplace_sub) == Latency;
-  if (r.ifuse && e.r4 && (t.ntt_ifuse_p == 2 || t.ntt_ifuse_p == 4)) r.tgroup = t.ntt_ifuse_p;
+  if (r.ifuse) r.tgroup = 2;
   return r;
 }
 
@@ -205,7 +194,7 @@ inline ModDownRoute moddown_route(const NttEnv& e, const NttTuning& t, int nc, i
   r.epi = !r.scatter ? NTT_EPI_SUBSCALE : aut == 2 ? NTT_EPI_SUBSCALE_AUT_ACC : NTT_EPI_SUBSCALE_AUT;
   if (r.bext_pro) {
     r.inv = inv_fwd_route(e, t, nc * B, e.K, level + 1, e.K, NTT_PRO_BEXT, r.epi, inplace_sub);
-    r.inv.rows_stored = producer_rows && t.mac_rows && e.r4 && r.inv.ifuse && !(aut && !r.scatter);
+    r.inv.rows_stored = producer_rows && t.mac_rows && r.inv.ifuse && !(aut && !r.scatter);
   }
   return r;
 }

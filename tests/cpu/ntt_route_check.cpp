@@ -22,8 +22,7 @@ struct Ctx {
 static const char* const TUNINGS[] = {"default", "ORION_BEXT_FUSE_BELOW=1024", "ORION_NTT_IFUSE=0",
                                       "ORION_NTT_AUT_FUSE=0", "ORION_NTT_IFUSE_MAXR=1000", "ORION_BEXT_FUSE=0",
                                       "ORION_MODUP_MERGE=0", "ORION_DEFER=0", "ORION_NTT2_TAIL_FWD=2",
-                                      "ORION_MAC_ROWS=0", "ORION_MAC_FWD_ROWS=0", "ORION_NTT_IFUSE_P=1",
-                                      "ORION_NTT_IMPL=2"};
+                                      "ORION_MAC_ROWS=0", "ORION_MAC_FWD_ROWS=0", "ORION_NTT_IMPL=2"};
 static const int NTUNING = sizeof(TUNINGS) / sizeof(TUNINGS[0]);
 static NttTuning tuning(int i) {
   NttTuning t;
@@ -38,14 +37,13 @@ static NttTuning tuning(int i) {
     case 8: t.ntt2_tail_fwd = 2; break;
     case 9: t.mac_rows = 0; break;
     case 10: t.mac_fwd_rows = 0; break;
-    case 11: t.ntt_ifuse_p = 1; break;
-    case 12: t.ntt_impl = 2; break;
+    case 11: t.ntt_impl = 2; break;
   }
   return t;
 }
 static NttEnv env(int logN, int ci, int K, int n_cu) {
   NttEnv e;
-  e.logN = logN, e.ci = ci != 0, e.K = K, e.n_cu = n_cu, e.r4 = true;
+  e.logN = logN, e.ci = ci != 0, e.K = K, e.n_cu = n_cu;
   e.max_limb = 64, e.max_src = 8, e.max_group = 64;
   return e;
 }
