@@ -374,6 +374,74 @@ void OrionHipDeleteLinearTransformBlocks(int blocks);
  * failed call allocates no handle. */
 int OrionHipMulRelinSum(const int *a, const int *b, int n);
 
+/* Complex packing: two real ciphertexts per bootstrap or linear layer.  Every
+ * value the frontend encrypts is real, a slot holds a complex number, and
+ * rotations, additions, MulPlaintext / EvaluateLinearTransform with real
+ * plaintexts and Bootstrap are linear over the reals slot by slot: applied to
+ * a + i b they give f(a) + i f(b).  So two images may share one ciphertext
+ * through the linear part of a network and through bootstrapping.
+ *
+ * Let I be the NTT of X^(N/2) over the Q limbs of the calling context's chain
+ * (X^(N/2) is +i on every slot: 5^j = 1 mod 4).  All arithmetic below is limb
+ * by limb mod q_j, on both components; o is the elementwise product.
+ *
+ *   OrionHipConjugateNew(ct)    = sigma_{2N-1}(ct): the key switch of ct.c1
+ *       with the Galois key of 2N-1, plus ct.c0, permuted (a rotation's
+ *       definition with that element).  Level, scale and batch are ct's.  The
+ *       key is made at first use when the scheme has the secret; without it
+ *       the key must have been loaded (LoadRotationKey(.., 2N-1) or the key
+ *       bundle), otherwise the call fails as a rotation without its key does.
+ *   OrionHipPackComplex(a, b)   = a + I o b at level = min(level a, level b),
+ *       one kernel launch.  The batches must be equal and the scales bit-equal
+ *       as long doubles (the rule of OrionHipStackCiphertexts: the error names
+ *       both handles and both values); the result has that scale.  a == b is
+ *       allowed.
+ *   OrionHipUnpackComplex(ct, out2): with yc = OrionHipConjugateNew(ct),
+ *       out2[0] = ct + yc         (= 2 Re)
+ *       out2[1] = I o (yc - ct)   (= -i (z - conj z) = 2 Im)
+ *       at ct's level and batch with scale = 2 * ct's scale (exact in long
+ *       double, no level consumed: two values at scale s are the values
+ *       themselves at scale 2s).  One conjugation key switch, then one kernel
+ *       launch that reads ct and yc once and writes both outputs.
+ *   OrionHipBootstrapPacked(ct, slots): a batch of B images refreshed by the
+ *       circuit run at batch h = ceil(B / 2).  Image k < B - h is packed with
+ *       image k + h on limb 0 (all Bootstrap reads); for odd B image h - 1
+ *       goes alone.  Bootstrap's circuit runs unchanged at batch h, and the
+ *       unpack at the residual top level writes images k and k + h of the
+ *       result.  Level L - 1, scale = 2 * the scale Bootstrap gives for the
+ *       same input scale.  For even B the result is bit-equal to
+ *       OrionHipSliceCiphertext of each half, OrionHipPackComplex, Bootstrap,
+ *       OrionHipUnpackComplex, OrionHipStackCiphertexts; with B = 1 it is
+ *       Bootstrap followed by ct + conj ct at twice the scale.  From a
+ *       pipeline thread it runs on the scheme's bootstrapper, as Bootstrap.
+ *
+ * What a packed ciphertext does NOT carry through:
+ *   - a real addend reaches only the real image: AddScalar and AddPlaintext
+ *     of a bias add to a, not to b.  Add biases after unpacking, at the
+ *     doubled scale;
+ *   - ct x ct products and EvaluatePolynomial mix the two images: unpack
+ *     before them;
+ *   - packing adds the two messages' coefficients, so the packed message
+ *     needs the same headroom under q_level as their sum;
+ *   - AddCiphertext's integer scale matching already handles an operand at
+ *     scale 2s against one at scale s.
+ *
+ * All four: the results are new handles of the calling thread's context; a
+ * pending deferred op runs first; an operand of another context is read like
+ * any foreign operand.  After one warm call (which makes the conjugation key)
+ * the first three may be captured into a graph; OrionHipBootstrapPacked, like
+ * Bootstrap, may not.
+ *
+ * Errors: -1 and OrionHipLastError for an unknown handle, a null out2,
+ * batches or scales that differ, a missing conjugation key, no bootstrapper
+ * for slots, a ConjugateInvariant scheme ("complex packing needs the Standard
+ * ring": its slots are real), and a poisoned source (its poison message).  A
+ * failed call allocates no handle and leaves out2 untouched. */
+int OrionHipConjugateNew(int ct);
+int OrionHipPackComplex(int a, int b);
+int OrionHipUnpackComplex(int ct, int *out2);
+int OrionHipBootstrapPacked(int ct, int slots);
+
 /* GPU encoder with device-resident slots (e.g. a torch tensor's data_ptr):
  * dvalues [batch][lenPerImage] float32; DecodeDevice writes the real parts of
  * all slots, [batch][N/2] float64, to device memory (asynchronous);

@@ -174,6 +174,10 @@ SIGNATURES = {
     "OrionHipEvaluateLinearTransformBlocks": ([c_int, P(c_int), c_int, P(c_int)], c_int),
     "OrionHipDeleteLinearTransformBlocks": ([c_int], None),
     "OrionHipMulRelinSum": ([P(c_int), P(c_int), c_int], c_int),
+    "OrionHipConjugateNew": ([c_int], c_int),
+    "OrionHipPackComplex": ([c_int, c_int], c_int),
+    "OrionHipUnpackComplex": ([c_int, P(c_int)], c_int),
+    "OrionHipBootstrapPacked": ([c_int, c_int], c_int),
     "ImportCiphertext": ([P(c_ulong), c_int, c_int, c_double], c_int),
     "ExportCiphertext": ([c_int, P(c_ulong), c_ulong], c_int),
     "ImportPlaintext": ([P(c_ulong), c_int, c_int, c_double], c_int),
@@ -565,6 +569,35 @@ class HipLibrary:
         self.lib.OrionHipClearError()
         h = self.lib.OrionHipMulRelinSum((c_int * len(a))(*a), (c_int * len(b))(*b), len(a))
         return self._chk(h, "OrionHipMulRelinSum")
+
+    # ---- complex packing (include/orion_hip.h) ---------------------------
+    def conjugate_new(self, ct):
+        """The complex conjugate of every slot, sigma_{2N-1}(ct), as a new
+        handle (OrionHipConjugateNew)."""
+        self.lib.OrionHipClearError()
+        return self._chk(self.lib.OrionHipConjugateNew(int(ct)), "OrionHipConjugateNew")
+
+    def pack_complex(self, a, b):
+        """a + i b as one new handle at the lower of the two levels
+        (OrionHipPackComplex): equal batches and scales required.  Real-linear
+        ops and Bootstrap act on both images; a real addend reaches only a."""
+        self.lib.OrionHipClearError()
+        return self._chk(self.lib.OrionHipPackComplex(int(a), int(b)), "OrionHipPackComplex")
+
+    def unpack_complex(self, ct):
+        """(re, im): the two images of a packed ciphertext as new handles at
+        twice ct's scale (OrionHipUnpackComplex)."""
+        out = (c_int * 2)(-1, -1)
+        self.lib.OrionHipClearError()
+        self._chk(self.lib.OrionHipUnpackComplex(int(ct), out), "OrionHipUnpackComplex")
+        return int(out[0]), int(out[1])
+
+    def bootstrap_packed(self, ct, slots):
+        """Bootstrap of a batch of B images with the circuit run at batch
+        ceil(B / 2) (OrionHipBootstrapPacked): a new batch of B refreshed
+        images at twice Bootstrap's scale."""
+        self.lib.OrionHipClearError()
+        return self._chk(self.lib.OrionHipBootstrapPacked(int(ct), int(slots)), "OrionHipBootstrapPacked")
 
     # Device-pointer calls run asynchronously on the library stream, which
     # torch does not know about: order them against the tensor's stream both

@@ -46,6 +46,10 @@ int orion_launch_tensor_sum(const LimbSet& d, const tsum::Table& T, bool acc, co
                             hipStream_t st);
 int orion_launch_gather(u64* dst, long long d_comp, long long d_limb, int nimg, int nlimb, const GatherTable& T,
                         int N, hipStream_t st);
+int orion_launch_pack_complex(const LimbSet& o, const LimbSet& a, const LimbSet& b, int npair, const u64* w4,
+                              const u64* w4s, const DeviceTables* tb, int N, hipStream_t st);
+int orion_launch_unpack_complex(const LimbSet& re, const LimbSet& im, const LimbSet& x, const LimbSet& y, int nim,
+                                const u64* w4, const u64* w4s, const DeviceTables* tb, int N, hipStream_t st);
 int orion_launch_basis_ext(const LimbSet& out, const LimbSet& in, const BasisExtTable* T, const DeviceTables* tb,
                            int N, hipStream_t st);
 int orion_launch_basis_ext_rescale(const LimbSet& out, const LimbSet& in, const BextRescaleTable* W, int N,
@@ -2250,6 +2254,68 @@ struct Context {
               nullptr, g, true);
   }
 
+  // -- complex packing (orion_hip.h Part 2) ---------------------------------
+  // Two real images share one ciphertext as a + i b: I = NTT(X^(N/2)) is i on
+  // every slot (5^j = 1 mod 4), and in the NTT domain it is w4 = psi^(N/2) on
+  // the first half of a limb, -w4 on the second (kernels.hip
+  // pack_complex_kernel), so the kernels take w4 per limb and read no table.
+  // w4 of every Q limb and its Shoup companion: made at first use, kept.
+  std::vector<u64> w4, w4s;
+  void need_complex() {
+    if (ci)
+      throw std::runtime_error("complex packing needs the Standard ring (a ConjugateInvariant slot holds a real number)");
+    if (!w4.empty()) return;
+    for (int j = 0; j < L; ++j) {
+      const u64 q = mods[j];
+      const u64 psi = hm_powmod(primitive_root(q), (q - 1) / nthroot, q);  // build_mod_tables' root
+      w4.push_back(hm_powmod(psi, (u64)N / 2, q));
+      w4s.push_back(hm_shoup(w4.back(), q));
+    }
+  }
+  void w4_of(const LimbSet& s, std::vector<u64>& w, std::vector<u64>& ws) const {
+    for (int l = 0; l < s.nlimb; ++l) {
+      if (s.mod[l] >= L) throw std::logic_error("complex packing runs on Q limbs");
+      w.push_back(w4[s.mod[l]]), ws.push_back(w4s[s.mod[l]]);
+    }
+  }
+  // o = a + I b on the images below npair, a alone on the rest; one launch
+  // (bytes: a and o per row, b on the paired rows)
+  void pack_launch(const LimbSet& o, const LimbSet& a, const LimbSet& b, int npair) {
+    std::vector<u64> w, ws;
+    w4_of(o, w, ws);
+    Scope sc(this, P_EW, 8.0 * N * o.ncomp * o.nlimb * (2 * o.nbatch + npair));
+    if (orion_launch_pack_complex(o, a, b, npair, w.data(), ws.data(), d_tb, N, stream))
+      throw std::runtime_error("pack_complex launch failed (batch or limb count out of range)");
+  }
+  // re = x + y, im = I (y - x) on the images below nim; one launch
+  void unpack_launch(const LimbSet& re, const LimbSet& im, const LimbSet& x, const LimbSet& y, int nim) {
+    std::vector<u64> w, ws;
+    w4_of(x, w, ws);
+    Scope sc(this, P_EW, 8.0 * N * x.ncomp * x.nlimb * (3 * x.nbatch + nim));
+    if (orion_launch_unpack_complex(re, im, x, y, nim, w.data(), ws.data(), d_tb, N, stream))
+      throw std::runtime_error("unpack_complex launch failed (batch or limb count out of range)");
+  }
+  // a + I b at the lower of the two levels (batches and scales equal: the caller checks)
+  Ciphertext pack_complex(const Ciphertext& a, const Ciphertext& b) {
+    need_complex();
+    const int level = std::min(a.level, b.level), B = a.poly.B;
+    Ciphertext o = new_ct(level, B, a.scale);
+    pack_launch(lsq(o.poly, 0, 2, level), lsq(a.poly, 0, 2, level), lsq(b.poly, 0, 2, level), B);
+    return o;
+  }
+  // (a + conj a, -i (a - conj a)) = twice the real and the imaginary image,
+  // held as the images themselves at twice the scale (exact, no level): the
+  // conjugation's key switch, then one launch
+  std::pair<Ciphertext, Ciphertext> unpack_complex(const Ciphertext& a) {
+    need_complex();
+    const int level = a.level, B = a.poly.B;
+    Ciphertext yc = apply_galois(a, 2 * (u64)N - 1);
+    Ciphertext re = new_ct(level, B, 2 * a.scale), im = new_ct(level, B, 2 * a.scale);
+    unpack_launch(lsq(re.poly, 0, 2, level), lsq(im.poly, 0, 2, level), lsq(a.poly, 0, 2, level),
+                  lsq(yc.poly, 0, 2, level), B);
+    return {std::move(re), std::move(im)};
+  }
+
   // scale matching for additions (Lattigo evaluateInPlace: the lower-scale
   // operand is multiplied by the rounded integer ratio when it is > 1)
   void add_like(Ciphertext& out, const Ciphertext& a, const LimbSet& b, long double bscale, int op) {
@@ -3506,6 +3572,34 @@ struct Context {
     }
     return out;
   }
+  // bootstrap of a batch of B images as h = ceil(B / 2) packed ones: image k <
+  // B - h rides with image k + h (for odd B image h - 1 goes alone).  The pack
+  // reads limb 0 only, as bootstrap does; the unpack at the residual top level
+  // writes its two outputs straight into the images k and k + h of the result,
+  // which holds the refreshed images at twice bootstrap's scale
+  Ciphertext bootstrap_packed(const Ciphertext& in, int ns) {
+    need_complex();
+    if (!btps.count(ns)) throw std::runtime_error("no bootstrapper found for slot count: " + std::to_string(ns));
+    const int B = in.poly.B, h = (B + 1) / 2, np = B - h;
+    Ciphertext p;
+    p.poly = alloc(2, 1, h);
+    p.level = 0;
+    p.scale = in.scale;
+    {
+      const LimbSet a = lsq(in.poly, 0, 2, 0, h);
+      LimbSet b = lsq(in.poly, 0, 2, 0, np);
+      b.p = np ? in.poly.ptr() + (long long)h * in.poly.batch_stride() : nullptr;
+      pack_launch(lsq(p.poly, 0, 2, 0), a, b, np);
+    }
+    const Ciphertext r = bootstrap(p, ns);
+    const Ciphertext yc = apply_galois(r, 2 * (u64)N - 1);
+    Ciphertext out = new_ct(r.level, B, 2 * r.scale);
+    const LimbSet re = lsq(out.poly, 0, 2, r.level, h);
+    LimbSet im = lsq(out.poly, 0, 2, r.level, np);
+    im.p = np ? out.poly.ptr() + (long long)h * out.poly.batch_stride() : nullptr;
+    unpack_launch(re, im, lsq(r.poly, 0, 2, r.level), lsq(yc.poly, 0, 2, r.level), np);
+    return out;
+  }
   void delete_bootstrappers() {
     if (stream) HIPCHK(hipStreamSynchronize(stream));
     btps.clear();
@@ -4706,6 +4800,52 @@ int OrionHipMulRelinSum(const int* a, const int* b, int n) {
   API_END(-1)
 }
 
+// ---- complex packing (orion_hip.h; Context::pack_complex) ----
+static const Ciphertext& complex_operand(Context& c, int id) {
+  const Ciphertext& x = c.cts.get(id);
+  if (!x.poly.ptr() || x.poly.ncomp < 2 || x.poly.nlimb < x.level + 1)
+    throw std::runtime_error("ciphertext " + std::to_string(id) + " holds no degree-1 polynomial pair");
+  return x;
+}
+int OrionHipConjugateNew(int ct) {
+  API_BEGIN
+  Context& c = ctx();
+  c.need_complex();
+  const Ciphertext& a = complex_operand(c, ct);
+  std::shared_ptr<Buffer> keep = a.poly.buf;  // the operand's buffer, until the launches are queued
+  return c.cts.add(c.apply_galois(a, 2 * (u64)c.N - 1));
+  API_END(-1)
+}
+int OrionHipPackComplex(int a, int b) {
+  API_BEGIN
+  Context& c = ctx();
+  c.need_complex();
+  const Ciphertext &x = complex_operand(c, a), &y = complex_operand(c, b);
+  if (x.poly.B != y.poly.B)
+    throw std::runtime_error("cannot pack ciphertexts " + std::to_string(a) + " (batch " + std::to_string(x.poly.B) +
+                             ") and " + std::to_string(b) + " (batch " + std::to_string(y.poly.B) +
+                             "): the batches differ");
+  if (x.scale != y.scale)
+    throw std::runtime_error("cannot pack ciphertexts " + std::to_string(a) + " (scale " + scale_str(x.scale) +
+                             ") and " + std::to_string(b) + " (scale " + scale_str(y.scale) + "): the scales differ");
+  std::shared_ptr<Buffer> keep[2] = {x.poly.buf, y.poly.buf};
+  return c.cts.add(c.pack_complex(x, y));
+  API_END(-1)
+}
+int OrionHipUnpackComplex(int ct, int* out2) {
+  API_BEGIN
+  Context& c = ctx();
+  c.need_complex();
+  if (!out2) throw std::runtime_error("null output handle pair");
+  const Ciphertext& a = complex_operand(c, ct);
+  std::shared_ptr<Buffer> keep = a.poly.buf;
+  std::pair<Ciphertext, Ciphertext> r = c.unpack_complex(a);
+  out2[0] = c.cts.add(std::move(r.first));
+  out2[1] = c.cts.add(std::move(r.second));
+  return 0;
+  API_END(-1)
+}
+
 // ---- linear transforms ----
 void NewLinearTransformEvaluator(void) {}
 
@@ -5153,11 +5293,18 @@ void NewBootstrapper(int* logPs, int n, int slots) {
 }
 // bootstrapper.go:61-80: a new ciphertext refreshed to the residual top level,
 // at the input's scale, post-scaled by 2^(LogMaxSlots - LogSlots)
-int Bootstrap(int ct, int slots) {
-  API_BEGIN
+// (packed: Context::bootstrap_packed in its place, OrionHipBootstrapPacked)
+static int bootstrap_handle(int ct, int slots, bool packed) {
   Context& c = ctx();
   Context* s = scheme_ctx();
-  if (c.btps.count(slots) || !s || s == &c) return c.cts.add(c.bootstrap(c.cts.get(ct), slots));
+  if (packed) c.need_complex();
+  auto run = [&](Context& on, const Ciphertext& in) {
+    if (!packed) return on.bootstrap(in, slots);
+    if (!in.poly.ptr() || in.poly.ncomp < 2)
+      throw std::runtime_error("ciphertext " + std::to_string(ct) + " holds no degree-1 polynomial pair");
+    return on.bootstrap_packed(in, slots);
+  };
+  if (c.btps.count(slots) || !s || s == &c) return c.cts.add(run(c, c.cts.get(ct)));
   // a pipeline bootstraps with the scheme's bootstrapper (one circuit and key
   // set per process), on the scheme's stream under the scheme's lock: the
   // scheme's stream waits for the input, the result is copied into a buffer
@@ -5170,7 +5317,7 @@ int Bootstrap(int ct, int slots) {
     Context* saved = t_act;
     t_act = s;
     try {
-      Ciphertext r = s->bootstrap(in, slots);
+      Ciphertext r = run(*s, in);
       out = c.new_ct(r.level, r.poly.B, r.scale);
       s->copy(s->lsq(out.poly, 0, 2, r.level), s->lsq(r.poly, 0, 2, r.level));
     } catch (...) {
@@ -5181,6 +5328,16 @@ int Bootstrap(int ct, int slots) {
   }
   wait_on(c, *s);
   return c.cts.add(std::move(out));
+}
+int Bootstrap(int ct, int slots) {
+  API_BEGIN
+  return bootstrap_handle(ct, slots, false);
+  API_END(-1)
+}
+// the batch refreshed two images per circuit run (orion_hip.h; Context::bootstrap_packed)
+int OrionHipBootstrapPacked(int ct, int slots) {
+  API_BEGIN
+  return bootstrap_handle(ct, slots, true);
   API_END(-1)
 }
 void DeleteBootstrappers(void) {

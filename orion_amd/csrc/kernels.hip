@@ -112,6 +112,66 @@ __global__ void __launch_bounds__(256) ew_kernel(LimbSet o, LimbSet a, LimbSet b
   *po = z;
 }
 
+// Complex packing (OrionHipPackComplex / OrionHipUnpackComplex).  I = NTT of
+// X^(N/2) is w4 = psi^(N/2) on the first half of a limb and -w4 on the second
+// (the forward NTT's output order puts psi^((2 br(j) + 1) N/2) at j, and
+// br(j) is odd exactly for j >= N/2), so it travels as one Shoup constant per
+// limb in the kernel arguments (sc.s, sc.ss) and no table is read.  Grid as
+// ew_kernel's: a thread's two coefficients lie in one half (N/2 is even).
+//
+// pack: o = a + I b on the images bi < npair; the images from npair on have
+// no partner and are copied (OrionHipBootstrapPacked's lone image)
+__global__ void __launch_bounds__(256) pack_complex_kernel(LimbSet o, LimbSet a, LimbSet b, Scalars sc, int npair,
+                                                           const DeviceTables* __restrict__ tb, int N) {
+  const int row = blockIdx.y;
+  const int bi = row % o.nbatch;
+  const int r = row / o.nbatch;
+  const int l = r % o.nlimb;
+  const int c = r / o.nlimb;
+  const int n = (blockIdx.x * kBlk + threadIdx.x) * 2;
+  if (n >= N) return;
+  const u64 q = tb->mc[arg_byte(o.mod, l)].q;
+  ulonglong2 z = *(const ulonglong2*)(a.p + row_off(a, c, l, bi) + n);
+  if (bi < npair) {
+    const ulonglong2 y = *(const ulonglong2*)(b.p + row_off(b, c, l, bi) + n);
+    const u64 w = sc.s[l], ws = sc.ss[l];
+    const u64 t0 = shoup_mul(y.x, w, ws, q), t1 = shoup_mul(y.y, w, ws, q);
+    if (n < N / 2) {
+      z.x = add_mod(z.x, t0, q);
+      z.y = add_mod(z.y, t1, q);
+    } else {
+      z.x = sub_mod(z.x, t0, q);
+      z.y = sub_mod(z.y, t1, q);
+    }
+  }
+  *(ulonglong2*)(o.p + row_off(o, c, l, bi) + n) = z;
+}
+
+// unpack: with y = conj x, re = x + y and im = I (y - x) = -i (x - conj x);
+// im is written for the images bi < nim only (the lone image has none).
+// Rows over x's (comp, limb, image); re and im have their own geometry
+__global__ void __launch_bounds__(256) unpack_complex_kernel(LimbSet re, LimbSet im, LimbSet x, LimbSet y, Scalars sc,
+                                                             int nim, const DeviceTables* __restrict__ tb, int N) {
+  const int row = blockIdx.y;
+  const int bi = row % x.nbatch;
+  const int r = row / x.nbatch;
+  const int l = r % x.nlimb;
+  const int c = r / x.nlimb;
+  const int n = (blockIdx.x * kBlk + threadIdx.x) * 2;
+  if (n >= N) return;
+  const u64 q = tb->mc[arg_byte(x.mod, l)].q;
+  const ulonglong2 u = *(const ulonglong2*)(x.p + row_off(x, c, l, bi) + n);
+  const ulonglong2 v = *(const ulonglong2*)(y.p + row_off(y, c, l, bi) + n);
+  *(ulonglong2*)(re.p + row_off(re, c, l, bi) + n) = make_ulonglong2(add_mod(u.x, v.x, q), add_mod(u.y, v.y, q));
+  if (bi >= nim) return;
+  const u64 w = sc.s[l], ws = sc.ss[l];
+  // -w4 d = w4 (-d): the second half multiplies x - y
+  const bool lo = n < N / 2;
+  const u64 d0 = lo ? sub_mod(v.x, u.x, q) : sub_mod(u.x, v.x, q);
+  const u64 d1 = lo ? sub_mod(v.y, u.y, q) : sub_mod(u.y, v.y, q);
+  *(ulonglong2*)(im.p + row_off(im, c, l, bi) + n) = make_ulonglong2(shoup_mul(d0, w, ws, q), shoup_mul(d1, w, ws, q));
+}
+
 // whole images gathered into a batch ciphertext: image i of the launch
 // (i < ORION_MAXGATHER) is copied from T.src[i] to dst + i*N, limb planes
 // (c, l), c < 2, l < nlimb, dst plane (c, l) at c*d_comp + l*d_limb.
@@ -1241,6 +1301,29 @@ int orion_launch_ew(int op, const LimbSet& o, const LimbSet& a, const LimbSet& b
 #undef CASE
     default: return -1;
   }
+  return 0;
+}
+
+// o = a + I b (images below npair; the rest a alone), w4/w4s: psi^(N/2) and
+// its Shoup companion per limb of o
+int orion_launch_pack_complex(const LimbSet& o, const LimbSet& a, const LimbSet& b, int npair, const u64* w4,
+                              const u64* w4s, const DeviceTables* tb, int N, hipStream_t st) {
+  const int rows = o.ncomp * o.nlimb * o.nbatch;
+  if (rows < 1 || rows > 65535 || N < 4 || (N & 3) || npair < 0 || npair > o.nbatch || (npair && !b.p)) return -1;
+  Scalars sc;
+  for (int l = 0; l < o.nlimb; ++l) sc.s[l] = w4[l], sc.ss[l] = w4s[l];
+  hipLaunchKernelGGL(pack_complex_kernel, ew_grid(N, rows), dim3(kBlk), 0, st, o, a, b, sc, npair, tb, N);
+  return 0;
+}
+
+// re = x + y, im = I (y - x) on the images below nim
+int orion_launch_unpack_complex(const LimbSet& re, const LimbSet& im, const LimbSet& x, const LimbSet& y, int nim,
+                                const u64* w4, const u64* w4s, const DeviceTables* tb, int N, hipStream_t st) {
+  const int rows = x.ncomp * x.nlimb * x.nbatch;
+  if (rows < 1 || rows > 65535 || N < 4 || (N & 3) || nim < 0 || nim > x.nbatch || (nim && !im.p)) return -1;
+  Scalars sc;
+  for (int l = 0; l < x.nlimb; ++l) sc.s[l] = w4[l], sc.ss[l] = w4s[l];
+  hipLaunchKernelGGL(unpack_complex_kernel, ew_grid(N, rows), dim3(kBlk), 0, st, re, im, x, y, sc, nim, tb, N);
   return 0;
 }
 
