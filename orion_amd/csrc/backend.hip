@@ -27,53 +27,11 @@
 #include "common.h"
 #include "deferral.h"
 #include "hostmath.h"
+#include "launch.h"
 #include "lt_blocks.h"
 #include "ntt_route.h"
 #include "tensor_sum.h"
 #include "wire.h"
-
-int orion_launch_ntt(int logN, const LimbSet& s, const DeviceTables* tb, bool inverse, hipStream_t st);
-int orion_launch_ntt_io(int logN, const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t st);
-int orion_launch_ntt2(int logN, const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t st);
-int orion_launch_ntt2s(int logN, const NttIO& io, const DeviceTables* tb, bool inverse, hipStream_t st,
-                       bool rows_only = false);
-int orion_ntt_init();
-int orion_launch_ew(int op, const LimbSet& o, const LimbSet& a, const LimbSet& b, const u64* s, const u64* ss,
-                    const DeviceTables* tb, int N, hipStream_t st);
-int orion_launch_tensor(const LimbSet& d, const LimbSet& a, const LimbSet& b, const DeviceTables* tb, int N,
-                        hipStream_t st);
-int orion_launch_tensor_sum(const LimbSet& d, const tsum::Table& T, bool acc, const DeviceTables* tb, int N,
-                            hipStream_t st);
-int orion_launch_gather(u64* dst, long long d_comp, long long d_limb, int nimg, int nlimb, const GatherTable& T,
-                        int N, hipStream_t st);
-int orion_launch_pack_complex(const LimbSet& o, const LimbSet& a, const LimbSet& b, int npair, const u64* w4,
-                              const u64* w4s, const DeviceTables* tb, int N, hipStream_t st);
-int orion_launch_unpack_complex(const LimbSet& re, const LimbSet& im, const LimbSet& x, const LimbSet& y, int nim,
-                                const u64* w4, const u64* w4s, const DeviceTables* tb, int N, hipStream_t st);
-int orion_launch_basis_ext(const LimbSet& out, const LimbSet& in, const BasisExtTable* T, const DeviceTables* tb,
-                           int N, hipStream_t st);
-int orion_launch_basis_ext_rescale(const LimbSet& out, const LimbSet& in, const BextRescaleTable* W, int N,
-                                   hipStream_t st);
-int orion_launch_modup_all(const LimbSet& D, const LimbSet& in, const BasisExtTable* Ts, int beta, int K,
-                           int nqp, const DeviceTables* tb, int N, hipStream_t st);
-int orion_launch_ks_mac(const LimbSet& out, const LimbSet& D, const LimbSet& own, const MacGroups& G, int ngroup,
-                        int beta, const DeviceTables* tb, int N, hipStream_t st);
-int orion_launch_automorph(const LimbSet& o, const LimbSet& a, const u32* idx, const DeviceTables* tb, int N,
-                           int accumulate, hipStream_t st);
-int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,
-                         const LtBabies& Bb, const LtPlan* plan, int chunk, int ne, int accumulate, bool one,
-                         const LimbSet& ptl, const DeviceTables* tb, int N, int colB, hipStream_t st);
-int orion_launch_lt_giant(const LimbSet& acc, const LimbSet& D, const LimbSet& own, const LimbSet& t0,
-                          const LimbSet& z, const LtGiants& G, const DeviceTables* tb, int N, hipStream_t st);
-
-int orion_launch_encode(const float* vals, int nvals, int B, double2* v, const double2* tw_inv, int logn, bool ci,
-                        const LimbSet& out, double scale, const DeviceTables* tb, hipStream_t st);
-int orion_launch_decode(const LimbSet& x, const u64* garner, double scale, int logn, bool ci, double2* v,
-                        const double2* tw_fwd, double* out, const DeviceTables* tb, hipStream_t st);
-int orion_launch_enc_sample(const LimbSet& r, const EncSampler& sp, const DeviceTables* tb, int N, hipStream_t st);
-int orion_launch_encode_c(double2* v, int B, const double2* tw_inv, int logn, bool ci, const LimbSet& out, double scale,
-                          const DeviceTables* tb, hipStream_t st);
-int orion_launch_modraise(const LimbSet& out, const LimbSet& in, const DeviceTables* tb, int N, hipStream_t st);
 
 namespace orion {
 struct LinTrans;
@@ -81,8 +39,6 @@ struct LinTrans;
 static std::vector<int> lt_bsgs_index(orion::LinTrans& T, int slots, int logRatio);
 
 namespace orion {
-
-enum { EW_ADD = 0, EW_SUB, EW_MUL, EW_MULADD, EW_NEG, EW_SCALE, EW_ADDC, EW_SUBSCALE, EW_COPY, EW_ADDSCALE, EW_SPLIT24 };
 
 #define HIPCHK(x)                                                                                  \
   do {                                                                                             \
@@ -1674,6 +1630,7 @@ struct Context {
     no_capture("evaluation key generation");
     const int beta = (level + 1 + K - 1) / K, nl = level + 1 + K;
     const std::vector<int> md = key_mods(level), kp = iota(0, nl);
+    const std::vector<u64> pq = p_mod_q(level);
     Poly k = alloc(2 * beta, nl, 1);
     Poly tmp = alloc(1, nl, 1);
     std::vector<u64> a((size_t)nl * N), e((size_t)nl * N);
@@ -1693,12 +1650,7 @@ struct Context {
       // + P * s_in on the Q limbs of digit i
       const int lo = i * K, hi = std::min((i + 1) * K, level + 1);
       std::vector<int> dl = iota(lo, hi);
-      std::vector<u64> pm;
-      for (int j : dl) {
-        u64 P = 1;
-        for (int kk = 0; kk < K; ++kk) P = hm_mulmod(P, mods[L + kk] % mods[j], mods[j]);
-        pm.push_back(P);
-      }
+      const std::vector<u64> pm(pq.begin() + lo, pq.begin() + hi);
       ew(EW_ADDSCALE, ls(k, 2 * i, 1, dl, dl), ls(s_in, 0, 1, dl, dl), ls(s_in, 0, 1, dl, dl), &pm);
     }
     return k;
@@ -2153,32 +2105,38 @@ struct Context {
     throw std::runtime_error("batch size mismatch");
   }
 
-  // keep_qp: as eval_lt's
+  // the relinearisation of a tensor d = (d0, d1, d2): (d0, d1) + keyswitch(d2),
+  // the addition folded into the gadget product.  keep_qp: as eval_lt's
+  Ciphertext relin_tail(const Poly& d, int level, int B, long double scale, bool keep_qp) {
+    const KeySwitchRoute r = ks_route(B, level, 0, keep_qp);
+    const bool pend = r.end == KsEnd::KeepQP;
+    Ciphertext out = pend ? pending_ct(level, B, scale) : new_ct(level, B, scale);
+    keyswitch(r, lsq(d, 2, 1, level), level, B, rlk, L - 1, pend ? out.pend : out.poly, d.ptr(),
+              d.ptr() + d.comp_stride());
+    return out;
+  }
+  // (tensor_kernel stays beside the one-pair tensor_sum_kernel, which computes
+  // the same d: MulRelinCiphertextNew was 1.4-1.5% slower through it in three
+  // of four cells, profiles/r14a_mul_relin_one_pair_ab.txt)
   Ciphertext mul_relin(const Ciphertext& a, const Ciphertext& b, bool keep_qp = false) {
     if (!have_rlk) throw std::runtime_error("relinearization key not generated");
     const int level = std::min(a.level, b.level);
     const int B = batch_of(a.poly.B, b.poly.B);
     Poly d = alloc(3, level + 1, B);
     {
-      LimbSet ld = lsq(d, 0, 3, level);
       // distinct bytes: both operands' 2 components and the 3 outputs; a
       // square (Quad's x * x, activation.py:55) reads one ciphertext
       const bool square = a.poly.ptr() == b.poly.ptr();
       Scope sc(this, P_TENSOR, 8.0 * N * (level + 1) * B * (square ? 5 : 7));
-      orion_launch_tensor(ld, lsq(a.poly, 0, 2, level, B), lsq(b.poly, 0, 2, level, B), d_tb, N, stream);
+      orion_launch_tensor(lsq(d, 0, 3, level), lsq(a.poly, 0, 2, level, B), lsq(b.poly, 0, 2, level, B), d_tb, N,
+                          stream);
     }
-    const KeySwitchRoute r = ks_route(B, level, 0, keep_qp);
-    const bool pend = r.end == KsEnd::KeepQP;
-    Ciphertext out = pend ? pending_ct(level, B, a.scale * b.scale) : new_ct(level, B, a.scale * b.scale);
-    // (d0, d1) + keyswitch(d2): the addition is folded into the gadget product
-    keyswitch(r, lsq(d, 2, 1, level), level, B, rlk, L - 1, pend ? out.pend : out.poly, d.ptr(),
-              d.ptr() + d.comp_stride());
-    return out;
+    return relin_tail(d, level, B, a.scale * b.scale, keep_qp);
   }
 
   // sum_i a[i] x b[i] with one relinearisation (tensor_sum.h): one tensor pass
   // accumulates (d0, d1, d2) over all pairs, ORION_MAXTSUM pairs per launch,
-  // then mul_relin's tail.  The operands' batches are B or 1 (checked by the
+  // then relin_tail.  The operands' batches are B or 1 (checked by the
   // caller); level = the minimum over the operands.  keep_qp: as eval_lt's
   Ciphertext mul_relin_sum(const std::vector<const Ciphertext*>& a, const std::vector<const Ciphertext*>& b, int level,
                            int B, long double scale, bool keep_qp = false) {
@@ -2210,49 +2168,35 @@ struct Context {
       Scope sc(this, P_TENSOR, 8.0 * N * (level + 1) * B * (4 * (cnt - T.nsq) + 2 * T.nsq + 3 + (c ? 3 : 0)));
       if (orion_launch_tensor_sum(ld, T, c > 0, d_tb, N, stream)) throw std::runtime_error("tensor sum launch failed");
     }
-    const KeySwitchRoute r = ks_route(B, level, 0, keep_qp);
-    const bool pend = r.end == KsEnd::KeepQP;
-    Ciphertext out = pend ? pending_ct(level, B, scale) : new_ct(level, B, scale);
-    keyswitch(r, lsq(d, 2, 1, level), level, B, rlk, L - 1, pend ? out.pend : out.poly, d.ptr(),
-              d.ptr() + d.comp_stride());
-    return out;
+    return relin_tail(d, level, B, scale, keep_qp);
   }
 
   Ciphertext rotate(const Ciphertext& a, int k) { return apply_galois(a, galois_element(k)); }
+  // out (acc: +)= sigma_g(a) = sigma_g((c0, 0) + keyswitch(c1)) with the Galois
+  // key of g: the c0 addition folded into the gadget product, the automorphism
+  // (an NTT-domain permutation) and the accumulation into the ModDown's store
+  void galois_switch(const Ciphertext& a, u64 g, Poly& out, bool acc) {
+    const int level = a.level, B = a.poly.B;
+    const EvKey& key = galois_key(g, level);
+    keyswitch(ks_route(B, level, acc ? 2 : 1), lsq(a.poly, 1, 1, level), level, B, key.k, key.level, out,
+              a.poly.ptr(), nullptr, g, acc);
+  }
   // sigma_{5^k}(a) into out's buffer (allocated here when it has none)
   void rotate_into(const Ciphertext& a, int k, Ciphertext& out) {
-    const u64 g = galois_element(k);
-    const int level = a.level, B = a.poly.B;
-    const EvKey& key = galois_key(g, level);
-    if (!out.poly.buf) out.poly = new_ct(level, B, a.scale).poly;
-    out.level = level;
-    keyswitch(ks_route(B, level, 1), lsq(a.poly, 1, 1, level), level, B, key.k, key.level, out.poly, a.poly.ptr(),
-              nullptr, g);
+    if (!out.poly.buf) out.poly = new_ct(a.level, a.poly.B, a.scale).poly;
+    out.level = a.level;
+    galois_switch(a, galois_element(k), out.poly, false);
   }
-  // sigma_g(a): key switch of c1 with the Galois key of g, + c0, NTT-domain permutation
-  // (g = 2N - 1 is the complex conjugation of the slots)
+  // sigma_g(a) (g = 2N - 1 is the complex conjugation of the slots)
   Ciphertext apply_galois(const Ciphertext& a, u64 g) {
-    const int level = a.level, B = a.poly.B;
-    const EvKey& key = galois_key(g, level);
-    // sigma_g((c0, 0) + keyswitch(c1)): the c0 addition folded into the gadget
-    // product, the automorphism into the ModDown's store
-    Ciphertext out = new_ct(level, B, a.scale);
-    keyswitch(ks_route(B, level, 1), lsq(a.poly, 1, 1, level), level, B, key.k, key.level, out.poly, a.poly.ptr(),
-              nullptr, g);
+    Ciphertext out = new_ct(a.level, a.poly.B, a.scale);
+    galois_switch(a, g, out.poly, false);
     return out;
   }
-
   // a += sigma_{5^k}(a), in place: RotateNew(a, k) followed by
-  // AddCiphertext(a, that rotation), with the addition in the ModDown's store
-  // (c1 is decomposed and c0 folded into the gadget product before the ModDown
-  // writes a)
-  void rotate_add_inplace(Ciphertext& a, int k) {
-    const u64 g = galois_element(k);
-    const int level = a.level, B = a.poly.B;
-    const EvKey& key = galois_key(g, level);
-    keyswitch(ks_route(B, level, 2), lsq(a.poly, 1, 1, level), level, B, key.k, key.level, a.poly, a.poly.ptr(),
-              nullptr, g, true);
-  }
+  // AddCiphertext(a, that rotation) (c1 is decomposed and c0 folded into the
+  // gadget product before the ModDown writes a)
+  void rotate_add_inplace(Ciphertext& a, int k) { galois_switch(a, galois_element(k), a.poly, true); }
 
   // -- complex packing (orion_hip.h Part 2) ---------------------------------
   // Two real images share one ciphertext as a + i b: I = NTT(X^(N/2)) is i on
@@ -2888,6 +2832,14 @@ struct Context {
     if (a > b) ++ls;
     return ls;
   }
+  // t <- 2 t + round(c): the Chebyshev doubling T_2j = 2 T_j^2 - 1 and
+  // EvalMod's double angle, c at t's scale (added to component 0)
+  void double_add_const(Ciphertext& t, long double c) {
+    const LimbSet lt = lsq(t.poly, 0, 2, t.level), l0 = lsq(t.poly, 0, 1, t.level);
+    ew(EW_ADD, lt, lt, lt);
+    const std::vector<u64> k = big_const_residues(c, t.level);
+    ew1(EW_ADDC, l0, l0, &k);
+  }
   const Ciphertext& poly_T(PolyRun& R, int j) {
     if (j == 1) return *R.x;
     if ((j & (j - 1)) == 0) return R.pw.at(j);
@@ -2897,17 +2849,14 @@ struct Context {
     const Ciphertext& A = poly_T(R, a);
     const Ciphertext& Bc = poly_T(R, b);
     Ciphertext t = mul_relin(A, Bc);
-    if (R.cheb) {
+    if (R.cheb && c == 0) {
+      double_add_const(t, -t.scale);
+    } else if (R.cheb) {
       const LimbSet lt = lsq(t.poly, 0, 2, t.level);
       ew(EW_ADD, lt, lt, lt);
-      if (c == 0) {
-        std::vector<u64> one = big_const_residues(-t.scale, t.level);
-        ew1(EW_ADDC, lsq(t.poly, 0, 1, t.level), lsq(t.poly, 0, 1, t.level), &one);
-      } else {
-        const Ciphertext& C = poly_T(R, c);
-        std::vector<u64> k = big_const_residues(-(t.scale / C.scale), t.level);
-        ew(EW_ADDSCALE, lt, lsq(C.poly, 0, 2, t.level), lt, &k);
-      }
+      const Ciphertext& C = poly_T(R, c);
+      std::vector<u64> k = big_const_residues(-(t.scale / C.scale), t.level);
+      ew(EW_ADDSCALE, lt, lsq(C.poly, 0, 2, t.level), lt, &k);
     }
     rescale_inplace(t);
     return R.baby.emplace(j, std::move(t)).first->second;
@@ -2993,12 +2942,7 @@ struct Context {
       const Ciphertext& a = s == 1 ? x : R.pw.at(s);
       Ciphertext t = mul_relin(a, a);
       rescale_inplace(t);
-      if (p.cheb) {
-        const LimbSet lt = lsq(t.poly, 0, 2, t.level);
-        ew(EW_ADD, lt, lt, lt);
-        std::vector<u64> one = big_const_residues(-t.scale, t.level);
-        ew1(EW_ADDC, lsq(t.poly, 0, 1, t.level), lsq(t.poly, 0, 1, t.level), &one);
-      }
+      if (p.cheb) double_add_const(t, -t.scale);
       R.pw.emplace(2 * s, std::move(t));
     }
     if (deg == 0) return poly_leaf(R, p.c, x.level, target);
@@ -3176,7 +3120,6 @@ struct Context {
     std::vector<LinTrans> cts, stc;  // in application order
     std::vector<u64> trace_gal;      // Galois elements of the trace (rotations by slots * 2^i)
     int top = 0;
-    Poly mono_i;          // n = N/2: NTT of X^(N/2) (x i on every slot), all Q limbs
     long double s_y = 0;  // scale of the EvalMod output (2^60 up to rounding)
     u64 F = 1;            // ScaleDown: message times F = round(q0 / (2^8 Delta)) before ModRaise
     EvKey d2s, s2d;       // EvkDenseToSparse (level 0), EvkSparseToDense (full chain)
@@ -3293,13 +3236,8 @@ struct Context {
         B->stc.push_back(make_lt_complex(M, level--));
       }
     }
-    if (!packed) {  // x i on every slot = multiplication by X^(N/2)
-      B->mono_i = alloc(1, L, 1);
-      std::vector<u64> host((size_t)L * N, 0);
-      for (int l = 0; l < L; ++l) host[(size_t)l * N + N / 2] = 1;
-      upload(B->mono_i, host);
-      ntt(lsq(B->mono_i, 0, 1, L - 1), false);
-    }
+    // x i on every slot = multiplication by X^(N/2): the packing kernels' w4
+    if (!packed) need_complex();
     B->need = key_needs(*B);
     // the keyed part; a context without the secret gets the circuit alone and
     // receives its keys record by record (import_key_record)
@@ -3400,14 +3338,6 @@ struct Context {
     HIPCHK(hipStreamSynchronize(stream));
   }
 
-  Ciphertext mul_i(const Bootstrapper& bt, const Ciphertext& a) {
-    Ciphertext o = new_ct(a.level, a.poly.B, a.scale);
-    LimbSet mi = ls(bt.mono_i, 0, 1, iota(0, a.level + 1), iota(0, a.level + 1), a.poly.B);
-    mi.ncomp = 2;
-    mi.comp_stride = 0;  // one plaintext for both components
-    ew(EW_MUL, lsq(o.poly, 0, 2, a.level), lsq(a.poly, 0, 2, a.level), mi);
-    return o;
-  }
   Ciphertext lt_rescale(LinTrans& T, const Ciphertext& x) {
     // (the final ModDown and the rescale as one division where that applies)
     Ciphertext y = eval_lt(T, x, true);
@@ -3425,10 +3355,7 @@ struct Context {
     Ciphertext y = eval_poly(u, bt.cosp, bt.t0);
     for (int k = 0; k < bt.r; ++k) {
       Ciphertext t = mul_relin(y, y);
-      const LimbSet lt = lsq(t.poly, 0, 2, t.level);
-      ew(EW_ADD, lt, lt, lt);
-      std::vector<u64> c = big_const_residues(-bt.dac[k] * t.scale, t.level);
-      ew1(EW_ADDC, lsq(t.poly, 0, 1, t.level), lsq(t.poly, 0, 1, t.level), &c);
+      double_add_const(t, -bt.dac[k] * t.scale);
       rescale_inplace(t);
       y = std::move(t);
     }
@@ -3471,14 +3398,13 @@ struct Context {
       ew(EW_ADD, lsq(u.poly, 0, 2, z.level), lsq(z.poly, 0, 2, z.level), lsq(zc.poly, 0, 2, z.level));
       y = eval_mod(bt, u);
     } else {
-      // real and imaginary parts: z + conj z, -i (z - conj z)
+      // real and imaginary parts: z + conj z, (conj z - z) i = -i (z - conj z)
       Ciphertext re = new_ct(z.level, B, z.scale), im = new_ct(z.level, B, z.scale);
-      ew(EW_ADD, lsq(re.poly, 0, 2, z.level), lsq(z.poly, 0, 2, z.level), lsq(zc.poly, 0, 2, z.level));
-      ew(EW_SUB, lsq(im.poly, 0, 2, z.level), lsq(zc.poly, 0, 2, z.level), lsq(z.poly, 0, 2, z.level));
-      im = mul_i(bt, im);  // (conj z - z) i = -i (z - conj z)
+      unpack_launch(lsq(re.poly, 0, 2, z.level), lsq(im.poly, 0, 2, z.level), lsq(z.poly, 0, 2, z.level),
+                    lsq(zc.poly, 0, 2, z.level), B);
       Ciphertext yr = eval_mod(bt, re), yi = eval_mod(bt, im);
-      y = mul_i(bt, yi);
-      ew(EW_ADD, lsq(y.poly, 0, 2, y.level), lsq(y.poly, 0, 2, y.level), lsq(yr.poly, 0, 2, y.level));
+      y = new_ct(yi.level, B, yi.scale);  // yr + i yi
+      pack_launch(lsq(y.poly, 0, 2, y.level), lsq(yr.poly, 0, 2, y.level), lsq(yi.poly, 0, 2, y.level), B);
     }
     // SlotsToCoeffs
     for (LinTrans& T : bt.stc) y = lt_rescale(T, y);
@@ -4546,8 +4472,7 @@ int ModDropCiphertext(int id) {
   API_END(-1)
 }
 
-static Ciphertext add_scalar(Context& c, const Ciphertext& a, float v, bool inplace_target, Ciphertext* dst) {
-  (void)inplace_target;
+static Ciphertext add_scalar(Context& c, const Ciphertext& a, float v, Ciphertext* dst) {
   std::vector<u64> k = c.scaled_const_residues(v, a.scale, a.level);
   Ciphertext o = dst ? Ciphertext() : c.new_ct(a.level, a.poly.B, a.scale);
   Ciphertext& out = dst ? *dst : o;
@@ -4559,14 +4484,14 @@ int AddScalar(int id, float v) {
   API_BEGIN
   Context& c = ctx();
   Ciphertext& a = c.inplace_ct(id);
-  add_scalar(c, a, v, true, &a);
+  add_scalar(c, a, v, &a);
   return id;
   API_END(-1)
 }
 int AddScalarNew(int id, float v) {
   API_BEGIN
   Context& c = ctx();
-  return c.cts.add(add_scalar(c, c.cts.get(id), v, false, nullptr));
+  return c.cts.add(add_scalar(c, c.cts.get(id), v, nullptr));
   API_END(-1)
 }
 int SubScalar(int id, float v) { return AddScalar(id, -v); }
@@ -4622,23 +4547,34 @@ int MulScalarFloatNew(int id, float v) {
   API_END(-1)
 }
 
+// The ciphertext side of a binary op, resolved against the other operand's
+// level and batch: a (made writable when in place), the result's level and
+// batch, and where the result goes -- a itself, or a new ciphertext that
+// done() registers
+struct BinaryOp {
+  Context& c;
+  const int id;
+  const bool inplace;
+  Ciphertext& a;
+  const int level, B;
+  Ciphertext o;
+  BinaryOp(Context& c_, int id_, int other_level, int other_B, bool inplace_)
+      : c(c_), id(id_), inplace(inplace_), a(inplace_ ? c_.inplace_ct(id_) : c_.cts.get(id_)),
+        level(std::min(a.level, other_level)), B(c_.batch_of(a.poly.B, other_B)) {
+    if (inplace && B != a.poly.B) throw std::runtime_error("in-place op cannot grow the batch");
+    if (!inplace) o = c.new_ct(level, B, a.scale);
+  }
+  Ciphertext& out() { return inplace ? a : o; }
+  int done() { return inplace ? id : c.cts.add(std::move(o)); }
+};
 // ct (+/-) pt
 static int ct_pt_op(int id, int pid, int op, bool inplace) {
   Context& c = ctx();
-  Ciphertext& a = inplace ? c.inplace_ct(id) : c.cts.get(id);
   const Plaintext& p = c.pts.get(pid);
-  const int level = std::min(a.level, p.level);
-  const int B = c.batch_of(a.poly.B, p.poly.B);
-  if (inplace && B != a.poly.B) throw std::runtime_error("in-place op cannot grow the batch");
-  Ciphertext o;
-  Ciphertext* out = &a;
-  if (!inplace) {
-    o = c.new_ct(level, B, a.scale);
-    out = &o;
-  }
-  out->level = level;
-  c.add_like(*out, a, c.lsq(p.poly, 0, 1, level, B), p.scale, op);
-  return inplace ? id : c.cts.add(std::move(o));
+  BinaryOp r(c, id, p.level, p.poly.B, inplace);
+  r.out().level = r.level;
+  c.add_like(r.out(), r.a, c.lsq(p.poly, 0, 1, r.level, r.B), p.scale, op);
+  return r.done();
 }
 int AddPlaintext(int id, int pt) {
   API_BEGIN
@@ -4662,24 +4598,15 @@ int SubPlaintextNew(int id, int pt) {
 }
 static int ct_pt_mul(int id, int pid, bool inplace) {
   Context& c = ctx();
-  Ciphertext& a = inplace ? c.inplace_ct(id) : c.cts.get(id);
   const Plaintext& p = c.pts.get(pid);
-  const int level = std::min(a.level, p.level);
-  const int B = c.batch_of(a.poly.B, p.poly.B);
-  if (inplace && B != a.poly.B) throw std::runtime_error("in-place op cannot grow the batch");
-  Ciphertext o;
-  Ciphertext* out = &a;
-  if (!inplace) {
-    o = c.new_ct(level, B, a.scale);
-    out = &o;
-  }
-  LimbSet lp = c.lsq(p.poly, 0, 1, level, B);
+  BinaryOp r(c, id, p.level, p.poly.B, inplace);
+  LimbSet lp = c.lsq(p.poly, 0, 1, r.level, r.B);
   lp.ncomp = 2;
   lp.comp_stride = 0;
-  c.ew(EW_MUL, c.lsq(out->poly, 0, 2, level), c.lsq(a.poly, 0, 2, level, B), lp);
-  out->level = level;
-  out->scale = a.scale * p.scale;
-  return inplace ? id : c.cts.add(std::move(o));
+  c.ew(EW_MUL, c.lsq(r.out().poly, 0, 2, r.level), c.lsq(r.a.poly, 0, 2, r.level, r.B), lp);
+  r.out().level = r.level;
+  r.out().scale = r.a.scale * p.scale;
+  return r.done();
 }
 int MulPlaintext(int id, int pt) {
   API_BEGIN
@@ -4693,20 +4620,11 @@ int MulPlaintextNew(int id, int pt) {
 }
 static int ct_ct_op(int i0, int i1, int op, bool inplace) {
   Context& c = ctx();
-  Ciphertext& a = inplace ? c.inplace_ct(i0) : c.cts.get(i0);
   const Ciphertext& b = c.cts.get(i1);
-  const int level = std::min(a.level, b.level);
-  const int B = c.batch_of(a.poly.B, b.poly.B);
-  if (inplace && B != a.poly.B) throw std::runtime_error("in-place op cannot grow the batch");
-  Ciphertext o;
-  Ciphertext* out = &a;
-  if (!inplace) {
-    o = c.new_ct(level, B, a.scale);
-    out = &o;
-  }
-  out->level = level;
-  c.add_like(*out, a, c.lsq(b.poly, 0, 2, level, B), b.scale, op);
-  return inplace ? i0 : c.cts.add(std::move(o));
+  BinaryOp r(c, i0, b.level, b.poly.B, inplace);
+  r.out().level = r.level;
+  c.add_like(r.out(), r.a, c.lsq(b.poly, 0, 2, r.level, r.B), b.scale, op);
+  return r.done();
 }
 int AddCiphertext(int a, int b) {
   API_BEGIN
@@ -5478,14 +5396,16 @@ long OrionHipBootstrapExport(int slots, int what, long arg, void* out, unsigned 
       if (out) export_evk_full(b, what == ORION_BTX_D2S ? bt.d2s : bt.s2d, (unsigned long*)out, n);
       return cnt;
     }
-    case ORION_BTX_MONO_I: {
-      if (!bt.mono_i.buf) throw std::runtime_error("sparse-slot circuit: no X^(N/2) plaintext");
-      const long cnt = (long)bt.mono_i.nlimb * b.N;
+    case ORION_BTX_MONO_I: {  // what the circuit multiplies by: w4 on the first half of a limb, -w4 on the second
+      if (bt.gap > 1) throw std::runtime_error("sparse-slot circuit: no X^(N/2) plaintext");
+      const long cnt = (long)b.L * b.N;
       if (out) {
         if (n != (unsigned long)cnt) throw std::runtime_error("export buffer size mismatch");
-        std::vector<u64> host;
-        b.download(bt.mono_i, host);
-        memcpy(out, host.data(), (size_t)cnt * 8);
+        u64* o = (u64*)out;
+        for (int l = 0; l < b.L; ++l) {
+          std::fill(o + (size_t)l * b.N, o + (size_t)l * b.N + b.N / 2, b.w4[l]);
+          std::fill(o + (size_t)l * b.N + b.N / 2, o + (size_t)(l + 1) * b.N, b.mods[l] - b.w4[l]);
+        }
       }
       return cnt;
     }

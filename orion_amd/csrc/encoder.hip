@@ -25,6 +25,7 @@
 #include <cstdio>
 
 #include "common.h"
+#include "launch.h"
 
 namespace {
 

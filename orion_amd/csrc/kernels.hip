@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 #include "ntt2s_rows.h"
 #include "tensor_sum.h"
 
@@ -41,21 +42,6 @@ __device__ __forceinline__ u64 gld(const u64* p, long long i) {
 __device__ __forceinline__ long long row_off(const LimbSet& s, int c, int l, int b) {
   return c * s.comp_stride + arg_byte(s.pos, l) * s.limb_stride + b * s.batch_stride;
 }
-
-enum EwOp : int {
-  EW_ADD = 0,      // o = a + b
-  EW_SUB = 1,      // o = a - b
-  EW_MUL = 2,      // o = a * b
-  EW_MULADD = 3,   // o = o + a * b
-  EW_NEG = 4,      // o = -a
-  EW_SCALE = 5,    // o = a * s_l            (Shoup scalar per limb)
-  EW_ADDC = 6,     // o = a + s_l            (constant per limb)
-  EW_SUBSCALE = 7, // o = (a - b) * s_l
-  EW_COPY = 8,     // o = a
-  EW_ADDSCALE = 9, // o = o + a * s_l
-  EW_SPLIT24 = 10, // o = split24(a) on limbs below 2^48, split30(a) on limbs up to 2^60, else a
-                   // (lt_bsgs's split-MAC operand forms)
-};
 
 struct Scalars {
   u64 s[ORION_MAXLIMB];

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "launch.h"
 #include "ntt_core.h"
 
 namespace {

@@ -21,6 +21,7 @@
 // Twiddles of the cols pass depend only on the row bits of the butterfly
 // group, identical for every column: they are wave-uniform scalar loads.
 #include "common.h"
+#include "launch.h"
 #include "ntt_arith.h"
 
 namespace {

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 #include "ntt_arith.h"
 #include "ntt2s_rows.h"
 

@@ -523,3 +523,21 @@ def test_poisoned_source_is_refused(torch_cuda):
         assert lib.GetCiphertextLevel(out) == 5
     finally:
         lib.DeleteScheme()
+
+
+# ---- the circuit's own multiplication by i ---------------------------------------------------------
+def test_exported_monomial_is_the_transform_of_the_monomial(env):
+    """the full-slot circuit multiplies by i with the packing kernels' constant and holds no plaintext for it;
+    bootstrap_export("mono_i") still answers with the NTT of X^(N/2) over the bootstrapping chain's Q primes,
+    limb by limb the oracle's forward transform, and a sparse circuit (which never multiplies by i) refuses"""
+    lib = env.lib
+    ns, boot, _ = env.bootstrapper(False)
+    nq = len(lib.bootstrap_moduli(ns)[0])
+    unit = np.zeros(N, dtype=np.uint64)
+    unit[N // 2] = 1
+    got = lib.bootstrap_export(ns, "mono_i")
+    assert got.shape == (nq * N,)
+    for j in range(nq):
+        assert np.array_equal(got[j * N:(j + 1) * N], boot.ntt(j, unit)), j
+    with pytest.raises(RuntimeError, match=r"sparse-slot circuit: no X\^\(N/2\) plaintext"):
+        lib.bootstrap_export(env.bootstrapper(True)[0], "mono_i")

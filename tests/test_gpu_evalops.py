@@ -415,6 +415,45 @@ def test_inplace_batch_refusals(env, Ba, msg):
 
 
 # ---------------------------------------------------------------------------
+# (c2) the plain product at the residues' maxima
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("level", [5, 0])
+@pytest.mark.parametrize("fill", ["max", "runs"])
+def test_mul_relin_planted_maxima(env, fill, level, B):
+    """MulRelinCiphertextNew and the in-place MulRelinCiphertext on imported
+    ciphertexts whose residues sit where the tensor's products and the sum of
+    two of them (d1) are largest: every residue q_j - 1, or random residues
+    under planted runs of 0, 1 and q_j - 1.  Two distinct operands (at B = 3
+    also a one-image second operand, broadcast) and one handle for both, the
+    square path.  The 60-bit q_0 is where a reduction has the least room.  Bit
+    for bit against the oracle's multiply and relinearise."""
+    lib = env.lib
+    rng = np.random.default_rng(360 + 10 * level + B)
+    s = 2.0 ** 40
+
+    def operand(b):
+        if fill == "runs":
+            return env.ct(rng, level, b)
+        q = np.array(env.mods[:level + 1], dtype=np.uint64)
+        return np.ascontiguousarray(np.broadcast_to((q - 1)[:, None], (b, 2, level + 1, env.N)))
+
+    x, y = operand(B), operand(B)
+    hx = env.imp(x, s)
+    seconds = [("a distinct operand", env.imp(y, s), y), ("one handle twice", hx, x)]
+    if B > 1:
+        seconds.append(("a one-image operand", env.imp(y[:1], s), y[:1]))
+    for what, hy, yv in seconds:
+        exp, es = ref_mul_relin(env, x, s, yv, s)
+        assert exp.shape == x.shape
+        env.check(env.keep(lib.MulRelinCiphertextNew(hx, hy)), exp, es, "MulRelinCiphertextNew, " + what)
+        t = env.keep(lib.CloneCiphertext(hx))
+        assert lib.MulRelinCiphertext(t, t if hy == hx else hy) == t
+        env.check(t, exp, es, "MulRelinCiphertext, " + what)
+    env.check(hx, x, s, "first operand")
+
+
+# ---------------------------------------------------------------------------
 # (d) scale matching
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("sa,sb", [(2.0 ** 60, 2.0 ** 40), (2.0 ** 40, 2.0 ** 60), (3 * 2.0 ** 40, 2.0 ** 40),
