@@ -214,6 +214,52 @@ int OrionHipSynchronize(void); /* drains every context's stream */
  * addition done in the key switch's final store.  The replay uses it when a
  * rotation's only consumer is that addition (LoLA's rotate-and-sum). */
 int OrionHipRotateAdd(int ct, int amount);
+/* Hoisted rotations: n rotations of one ciphertext from one gadget
+ * decomposition (Lattigo's RotateHoisted).  A rotation's key switch decomposes
+ * c1 (an INTT, the ModUps, the forward NTTs), takes one gadget product and one
+ * ModDown; the decomposition depends on the ciphertext alone, so it is computed
+ * once here where n RotateNew calls compute it n times.
+ *
+ * 1 <= n <= 64.  amounts[i] is read as RotateNew reads its amount
+ * (GaloisElement(amounts[i])): negative amounts, amounts >= slots and
+ * duplicates are fine.  out[i] is a new handle of the calling thread's context
+ * with ct's level, scale and batch, and its bits are equal to
+ * RotateNew(ct, amounts[i]): the arithmetic is RotateNew's own -- the same
+ * decomposition, the same gadget product with c0 folded in as P c0, the same
+ * ModDown whose store applies the automorphism, once per output.  An amount
+ * whose Galois element is 1 gives a copy of ct (CloneCiphertext's bits): it
+ * needs no key and runs no key switch.  The gadget products of up to 16 keys
+ * run as one launch that reads the decomposition once.
+ *
+ * A pending deferred op runs first; a source of another context is read like
+ * any foreign operand; every key is made or checked (at ct's level, as
+ * RotateNew does: a scheme without the secret fails with Rotate's message, a
+ * pipeline takes its keys from the scheme) before anything is allocated; after
+ * one warm call the call may be captured into a graph (the key table travels in
+ * the kernel arguments).
+ *
+ * Errors: -1 and OrionHipLastError for a null amounts or out, n < 1 or n > 64
+ * (the number and the limit are named), an unknown handle, a handle without a
+ * degree-1 pair, a missing key, and a poisoned source (its poison message).  A
+ * failed call allocates no handle and leaves out untouched.  Returns 0. */
+int OrionHipRotateHoisted(int ct, const int *amounts, int n, int *out);
+/* The sum of n rotations of one ciphertext: one decomposition, n gadget
+ * products, one ModDown, where the loop of RotateNew / AddCiphertext runs n of
+ * each.  Amounts, n, keys, the pending op, foreign sources, graph capture and
+ * errors are OrionHipRotateHoisted's; a repeated amount counts as often as it
+ * appears.  Returns a new handle of the calling thread's context with ct's
+ * level, scale and batch, or -1.
+ *
+ * ModDown of a sum is not the sum of ModDowns, and the automorphisms are
+ * applied in QP, so the result differs in its last bits from that loop, even
+ * for n = 1; it has its own exact definition.  With level = ct's level, QP =
+ * the limbs 0..level and the P limbs, g_i = GaloisElement(amounts[i]):
+ *
+ *   D    = gadget decomposition of ct.c1
+ *   r_i  = sigma_{g_i}( gadget(D, key_{g_i}) + (P ct.c0, 0) )   in QP, g_i != 1
+ *   r_i  = P ct on the Q limbs (P mod q_j), 0 on the P limbs    g_i = 1
+ *   out  = ModDown( sum_i r_i ) */
+int OrionHipRotateSum(int ct, const int *amounts, int n);
 int OrionHipGraphBegin(void);
 int OrionHipGraphEnd(void);                               /* graph id, or -1 */
 int OrionHipGraphLaunch(int graph);

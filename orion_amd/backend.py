@@ -87,6 +87,8 @@ SIGNATURES = {
     "Rotate": ([c_int, c_int], c_int),
     "RotateNew": ([c_int, c_int], c_int),
     "OrionHipRotateAdd": ([c_int, c_int], c_int),
+    "OrionHipRotateHoisted": ([c_int, P(c_int), c_int, P(c_int)], c_int),
+    "OrionHipRotateSum": ([c_int, P(c_int), c_int], c_int),
     "Rescale": ([c_int], c_int),
     "RescaleNew": ([c_int], c_int),
     "AddScalar": ([c_int, c_float], c_int),
@@ -569,6 +571,29 @@ class HipLibrary:
         self.lib.OrionHipClearError()
         h = self.lib.OrionHipMulRelinSum((c_int * len(a))(*a), (c_int * len(b))(*b), len(a))
         return self._chk(h, "OrionHipMulRelinSum")
+
+    # ---- hoisted rotations (include/orion_hip.h) -------------------------
+    def rotate_hoisted(self, ct, amounts):
+        """The rotations of ct by every amount, from one decomposition
+        (OrionHipRotateHoisted): a list of new handles, each bit-equal to
+        RotateNew(ct, amount).  1 to 64 amounts; duplicates, negative amounts
+        and 0 (a copy) are fine."""
+        k = [int(a) for a in amounts]
+        out = (c_int * max(len(k), 1))()
+        self.lib.OrionHipClearError()
+        rc = self.lib.OrionHipRotateHoisted(int(ct), (c_int * max(len(k), 1))(*k), len(k), out)
+        self._chk(rc, "OrionHipRotateHoisted")
+        return [int(h) for h in out[:len(k)]]
+
+    def rotate_sum(self, ct, amounts):
+        """The sum of the rotations of ct by every amount as one new handle
+        (OrionHipRotateSum): one decomposition and one ModDown; a repeated
+        amount counts as often as it appears.  The last bits differ from the
+        loop of RotateNew / AddCiphertext (the header has the definition)."""
+        k = [int(a) for a in amounts]
+        self.lib.OrionHipClearError()
+        h = self.lib.OrionHipRotateSum(int(ct), (c_int * max(len(k), 1))(*k), len(k))
+        return self._chk(h, "OrionHipRotateSum")
 
     # ---- complex packing (include/orion_hip.h) ---------------------------
     def conjugate_new(self, ct):

@@ -2198,6 +2198,140 @@ struct Context {
   // gadget product before the ModDown writes a)
   void rotate_add_inplace(Ciphertext& a, int k) { galois_switch(a, galois_element(k), a.poly, true); }
 
+  // -- hoisted rotations (orion_hip.h Part 2; hoist.h) ------------------------
+  // sigma_g(a) for every g of gs, from one decomposition of a.c1: per chunk of
+  // ORION_MAXHOIST rotating elements one gadget-product launch over all its
+  // keys (ks_mac_hoisted_kernel; past hoist::in_registers the grouped ks_mac
+  // with the shared decomposition) into a QP scratch [chunk][2][QP][B], then
+  // one ModDown per output whose store applies the automorphism.  The
+  // arithmetic is galois_switch's, so every output has its bits.  g = 1: a
+  // copy of a.  Every key is made or checked before anything is allocated.
+  std::vector<Ciphertext> rotate_hoisted(const Ciphertext& a, const std::vector<u64>& gs) {
+    const int level = a.level, B = a.poly.B, nqp = level + 1 + K, beta = (level + 1 + K - 1) / K;
+    std::vector<int> rot;  // the outputs that rotate
+    for (size_t i = 0; i < gs.size(); ++i)
+      if (gs[i] != 1) galois_key(gs[i], level), rot.push_back((int)i);
+    std::vector<Ciphertext> out(gs.size());
+    for (size_t i = 0; i < gs.size(); ++i)
+      if (gs[i] == 1) out[i] = clone(a);
+    const int nr = (int)rot.size();
+    if (nr == 0) return out;
+    const HoistRoute r = hoist_route(env, tun, B, level, false);
+    const LimbSet c0 = lsq(a.poly, 0, 1, level), c1 = lsq(a.poly, 1, 1, level);
+    Poly D = decompose(c1, level, B, r.dec);
+    const LimbSet dl = lsqp(D, 0, beta, level, level);
+    Poly u = alloc(2 * std::min(nr, ORION_MAXHOIST), nqp, B);  // reused by every chunk (stream order)
+    const LimbSet uq = lsqp(u, 0, 2, level, level);
+    const long long gstride = 2 * u.comp_stride();
+    const std::vector<u64> pq = p_mod_q(level);
+    for (int c = 0; c < hoist::launches(nr); ++c) {
+      const int first = hoist::chunk_first(c), cnt = hoist::chunk_count(nr, c);
+      if (hoist::in_registers(beta)) {
+        MacHoist H;
+        memset(&H, 0, sizeof(H));
+        for (int k = 0; k < cnt; ++k) {
+          const EvKey& kk = gks.at(gs[rot[first + k]]);
+          H.keys.key[k] = kk.k.ptr(), H.keys.klvl[k] = kk.level;
+        }
+        H.keys.n = cnt;
+        H.L = L, H.K = K, H.beta = beta;
+        H.out_gstride = gstride;
+        for (int j = 0; j <= level; ++j) H.add_s[j] = pq[j], H.add_ss[j] = hm_shoup(pq[j], mods[j]);
+        // per row: the decomposition (beta digits, once for all keys), the c0
+        // addend on the Q limbs, every key's output pair; per QP limb: each
+        // key (2 beta)
+        const double rows = (double)nqp * B;
+        Scope sc(this, P_MAC, 8.0 * N * (rows * (beta + 2.0 * cnt) + (double)(level + 1) * B +
+                                         (double)nqp * 2.0 * beta * cnt));
+        if (orion_launch_ks_mac_hoisted(uq, dl, c1, c0, H, d_tb, N, stream))
+          throw std::runtime_error("ks_mac_hoisted launch failed");
+      } else {
+        std::vector<const u64*> keys;
+        std::vector<int> klvl;
+        for (int k = 0; k < cnt; ++k) {
+          const EvKey& kk = gks.at(gs[rot[first + k]]);
+          keys.push_back(kk.k.ptr()), klvl.push_back(kk.level);
+        }
+        mac_groups(uq, gstride, dl, 0, c1, 0, keys, klvl, beta, a.poly.ptr(), 0, level + 1);
+      }
+      for (int k = 0; k < cnt; ++k) {
+        Ciphertext o = new_ct(level, B, a.scale);
+        moddown(lsqp(u, 2 * k, 2, level, level), level, lsq(o.poly, 0, 2, level), r.out_md, gs[rot[first + k]]);
+        out[rot[first + k]] = std::move(o);
+      }
+    }
+    return out;
+  }
+  // ModDown( sum_i r_i ) over the elements g_i of gs (orion_hip.h
+  // OrionHipRotateSum), r_i = sigma_{g_i}( gadget(D, key_{g_i}) + (P c0, 0) )
+  // in QP, or P a on the Q limbs where g_i = 1: one decomposition, the gadget
+  // products and automorphisms summed in QP by one lt_giant launch whose giants
+  // share the decomposition (group strides 0), one ModDown.  Every key is made
+  // or checked before anything is allocated.
+  Ciphertext rotate_sum(const Ciphertext& a, const std::vector<u64>& gs) {
+    const int level = a.level, B = a.poly.B, nqp = level + 1 + K, beta = (level + 1 + K - 1) / K;
+    if (gs.size() > ORION_MAXGROUP) throw std::runtime_error("rotate_sum: too many Galois elements for one launch");
+    std::vector<u64> rot;
+    u64 nid = 0;  // how often the identity appears
+    for (u64 g : gs) {
+      if (g == 1)
+        ++nid;
+      else
+        galois_key(g, level), rot.push_back(g);
+    }
+    const HoistRoute r = hoist_route(env, tun, B, level, !rot.empty());
+    LtGiants G;
+    memset(&G, 0, sizeof(G));
+    for (size_t k = 0; k < rot.size(); ++k) {  // (every key exists: gen_galois may replace one)
+      const EvKey& kk = gks.at(rot[k]);
+      G.key[k] = kk.k.ptr(), G.klvl[k] = kk.level, G.idx[k] = aut_index(rot[k]);
+    }
+    Ciphertext out = new_ct(level, B, a.scale);
+    const std::vector<u64> pq = p_mod_q(level);
+    // nid P a on the Q limbs, zeros on the P limbs: the sum itself without a
+    // rotating term, lt_giant's zero giant with one
+    Poly zp;
+    LimbSet z;
+    if (nid) {
+      zp = alloc(2, nqp, B);
+      z = lsqp(zp, 0, 2, level, level);
+      std::vector<u64> s;
+      for (int j = 0; j <= level; ++j) s.push_back(hm_mulmod(pq[j], nid % mods[j], mods[j]));
+      HIPCHK(hipMemsetAsync(zp.ptr(), 0, (size_t)2 * nqp * B * N * sizeof(u64), stream));
+      ew1(EW_SCALE, lsq(zp, 0, 2, level), lsq(a.poly, 0, 2, level), &s);
+    }
+    if (rot.empty()) {
+      moddown(z, level, lsq(out.poly, 0, 2, level), r.sum_md);
+      return out;
+    }
+    Poly D = decompose(lsq(a.poly, 1, 1, level), level, B, r.dec);
+    // P c0 on the Q limbs, zeros on the P limbs (lt_giant reads every QP limb of t0)
+    Poly t0 = alloc(1, nqp, B);
+    HIPCHK(hipMemsetAsync(t0.ptr(), 0, (size_t)nqp * B * N * sizeof(u64), stream));
+    ew1(EW_SCALE, lsq(t0, 0, 1, level), lsq(a.poly, 0, 1, level), &pq);
+    Poly acc = alloc(2, nqp, B);
+    const LimbSet la = lsqp(acc, 0, 2, level, level);
+    G.ng = (int)rot.size();
+    G.beta = beta, G.K = K, G.level = level, G.L = L;
+    G.has_zero = nid ? 1 : 0;
+    G.xcd = lt_xcd && (N / 256) % 8 == 0;
+    G.rows_from = r.sum_md.inv.rows_stored ? level + 1 : 0;
+    G.logN = logN;
+    G.d_gstride = G.own_gstride = G.t0_gstride = 0;
+    {
+      // per row: the decomposition (beta digits) and the t0 term once, the
+      // output pair and the identity's pair; per QP limb: each key (2 beta)
+      const double rows = (double)nqp * B;
+      Scope sc(this, P_LTGIANT,
+               8.0 * N * (rows * (beta + 1.0 + 2.0 + 2.0 * G.has_zero) + (double)nqp * 2.0 * beta * G.ng));
+      if (orion_launch_lt_giant(la, lsqp(D, 0, 1, level, level), lsq(a.poly, 1, 1, level),
+                                lsqp(t0, 0, 1, level, level), nid ? z : la, G, d_tb, N, stream))
+        throw std::runtime_error("lt_giant launch failed");
+    }
+    moddown(la, level, lsq(out.poly, 0, 2, level), r.sum_md);
+    return out;
+  }
+
   // -- complex packing (orion_hip.h Part 2) ---------------------------------
   // Two real images share one ciphertext as a + i b: I = NTT(X^(N/2)) is i on
   // every slot (5^j = 1 mod 4), and in the NTT domain it is w4 = psi^(N/2) on
@@ -4436,6 +4570,40 @@ int OrionHipRotateAdd(int id, int k) {
   Context& c = ctx();
   c.rotate_add_inplace(c.inplace_ct(id), k);
   return id;
+  API_END(-1)
+}
+// ---- hoisted rotations (orion_hip.h; Context::rotate_hoisted, rotate_sum) ----
+// the checks both calls share; the Galois elements of the amounts into gs
+static const Ciphertext& hoist_source(Context& c, int ct, const int* amounts, int n, std::vector<u64>& gs) {
+  if (!amounts) throw std::runtime_error("null amount list");
+  if (n < 1 || n > ORION_MAXGROUP)
+    throw std::runtime_error("cannot rotate by " + std::to_string(n) + " amounts in one call: 1 to " +
+                             std::to_string(ORION_MAXGROUP) + " are accepted");
+  const Ciphertext& a = c.cts.get(ct);
+  if (!a.poly.ptr() || a.poly.ncomp < 2 || a.poly.nlimb < a.level + 1)
+    throw std::runtime_error("ciphertext " + std::to_string(ct) + " holds no degree-1 polynomial pair");
+  for (int i = 0; i < n; ++i) gs.push_back(c.galois_element(amounts[i]));
+  return a;
+}
+int OrionHipRotateHoisted(int ct, const int* amounts, int n, int* out) {
+  API_BEGIN
+  Context& c = ctx();
+  if (!out) throw std::runtime_error("null output list");
+  std::vector<u64> gs;
+  const Ciphertext& a = hoist_source(c, ct, amounts, n, gs);
+  std::shared_ptr<Buffer> keep = a.poly.buf;  // the operand's buffer, until the launches are queued
+  std::vector<Ciphertext> r = c.rotate_hoisted(a, gs);
+  for (int i = 0; i < n; ++i) out[i] = c.cts.add(std::move(r[i]));
+  return 0;
+  API_END(-1)
+}
+int OrionHipRotateSum(int ct, const int* amounts, int n) {
+  API_BEGIN
+  Context& c = ctx();
+  std::vector<u64> gs;
+  const Ciphertext& a = hoist_source(c, ct, amounts, n, gs);
+  std::shared_ptr<Buffer> keep = a.poly.buf;  // the operand's buffer, until the launches are queued
+  return c.cts.add(c.rotate_sum(a, gs));
   API_END(-1)
 }
 // Rescale / RescaleNew of handle id: when its ModDown is what is pending,

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ntt_consts.h"
+#include "hoist.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -270,6 +271,17 @@ struct MacGroups {  // ks_mac_kernel: group g uses key[g], made for level klvl[g
   // D hold its forward NTT's columns-pass intermediate; the gadget product
   // runs their forward rows pass itself, in LDS, before the products
   int fwd_rows;
+};
+
+// ks_mac_hoisted_kernel: the gadget products of one decomposition with the
+// keys of H.keys (hoist.h), output g's comps 0/1 at out.p + g*out_gstride.
+// add_s / add_ss: P mod q_l and its Shoup companion on the addend's limbs
+// (MacGroups' add_nq form: the ModDown that follows yields keyswitch + add)
+struct MacHoist {
+  hoist::Keys keys;
+  int L, K, beta;  // Q moduli of the chain, digit width, digits
+  long long out_gstride;
+  u64 add_s[ORION_MAXLIMB], add_ss[ORION_MAXLIMB];
 };
 
 // gather of whole images into a batch ciphertext (gather_images_kernel:

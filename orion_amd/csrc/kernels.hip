@@ -670,6 +670,82 @@ __global__ void __launch_bounds__(256) ks_mac_full_kernel(LimbSet out, LimbSet D
   ks_mac_body<true, true, PRE>(out, D, own, G, beta, tb, N, lds_dyn);
 }
 
+// Gadget products of one decomposition with many keys (hoisted rotations,
+// Context::rotate_hoisted):
+//   out_g,c[j] = P*add[j]*(c == 0) + sum_i D_i[j] * key_g[i][c][mod_j]   (c = 0, 1)
+// for every key g of H.keys.  A thread owns two adjacent coefficients of one
+// (limb, image) row: it loads the beta digit words once (digit i's own Q limbs
+// from `own`, as ks_mac_body) and forms P*add once, then loops over the keys:
+// 2 beta key words, the split MAC in chunks of KS_CH digits, both components
+// stored.  ks_mac_kernel with the keys as groups reads the beta rows of D once
+// per key.  HB: the digit slots held in registers (beta <= HB).  The results
+// are ks_mac_kernel's bit for bit: both are exact mod q and fully reduced.
+template <int HB>
+__global__ void __launch_bounds__(256) ks_mac_hoisted_kernel(LimbSet out, LimbSet D, LimbSet own, LimbSet add,
+                                                             MacHoist H, const DeviceTables* __restrict__ tb, int N) {
+  const int row = blockIdx.y;
+  const int bi = row % out.nbatch;
+  const int l = row / out.nbatch;
+  const int n = (blockIdx.x * kBlk + threadIdx.x) * 2;
+  if (n >= N) return;
+  const int m = arg_byte(out.mod, l);
+  const ModConst mc = tb->mc[m];
+  const u64 q = mc.q;
+  const int beta = H.beta;
+  const int owndigit = l < own.nlimb ? l / H.K : -1;
+  ulonglong2 d[HB];
+#pragma unroll
+  for (int u = 0; u < HB; ++u) {
+    if (u < beta)
+      d[u] = u == owndigit ? *(const ulonglong2*)(own.p + row_off(own, 0, l, bi) + n)
+                           : *(const ulonglong2*)(D.p + row_off(D, u, l, bi) + n);
+  }
+  ulonglong2 a0 = make_ulonglong2(0, 0);
+  if (l < add.nlimb) {  // a Q limb: P * add (the P limbs get 0)
+    const ulonglong2 a = *(const ulonglong2*)(add.p + row_off(add, 0, l, bi) + n);
+    const u64 s = H.add_s[l], ss = H.add_ss[l];
+    a0 = make_ulonglong2(shoup_mul(a.x, s, ss, q), shoup_mul(a.y, s, ss, q));
+  }
+  const long long o0 = row_off(out, 0, l, bi) + n, o1 = row_off(out, 1, l, bi) + n;
+  for (int g = 0; g < H.keys.n; ++g) {  // (uniform)
+    const int kl = H.keys.klvl[g];
+    const long long kstride = (long long)(kl + 1 + H.K) * N;
+    const u64* kp = H.keys.key[g] + (long long)key_pos(m, H.L, kl) * N + n;
+    ulonglong2 r0 = a0, r1 = make_ulonglong2(0, 0);
+#pragma unroll
+    for (int i0 = 0; i0 < HB; i0 += KS_CH) {
+      if (i0 < beta) {
+        ulonglong2 kb[KS_CH], ka[KS_CH];
+#pragma unroll
+        for (int u = 0; u < KS_CH; ++u) {
+          if (i0 + u < beta) {
+            kb[u] = *(const ulonglong2*)(kp + (2 * (i0 + u) + 0) * kstride);
+            ka[u] = *(const ulonglong2*)(kp + (2 * (i0 + u) + 1) * kstride);
+          }
+        }
+        MacAcc s0x, s0y, s1x, s1y;
+        mac_zero(s0x), mac_zero(s0y), mac_zero(s1x), mac_zero(s1y);
+#pragma unroll
+        for (int u = 0; u < KS_CH; ++u) {
+          if (i0 + u < beta) {
+            mac_add(s0x, d[i0 + u].x, kb[u].x);
+            mac_add(s0y, d[i0 + u].y, kb[u].y);
+            mac_add(s1x, d[i0 + u].x, ka[u].x);
+            mac_add(s1y, d[i0 + u].y, ka[u].y);
+          }
+        }
+        r0.x = add_mod(r0.x, mac_reduce(s0x, mc), q);
+        r0.y = add_mod(r0.y, mac_reduce(s0y, mc), q);
+        r1.x = add_mod(r1.x, mac_reduce(s1x, mc), q);
+        r1.y = add_mod(r1.y, mac_reduce(s1y, mc), q);
+      }
+    }
+    u64* op = out.p + g * H.out_gstride;
+    *(ulonglong2*)(op + o0) = r0;
+    *(ulonglong2*)(op + o1) = r1;
+  }
+}
+
 // NTT-domain automorphism: o[j] = a[idx[j]]  (optionally o += a[idx[j]])
 __global__ void __launch_bounds__(256) automorph_kernel(LimbSet o, LimbSet a, const u32* __restrict__ idx,
                                                         const DeviceTables* __restrict__ tb, int N, int accumulate) {
@@ -1429,6 +1505,22 @@ int orion_launch_ks_mac(const LimbSet& out, const LimbSet& D, const LimbSet& own
     return 0;
   }
   hipLaunchKernelGGL(ks_mac_kernel, ew_grid(N, rows), dim3(256), 0, st, out, D, own, G, beta, tb, N);
+  return 0;
+}
+
+int orion_launch_ks_mac_hoisted(const LimbSet& out, const LimbSet& D, const LimbSet& own, const LimbSet& add,
+                                const MacHoist& H, const DeviceTables* tb, int N, hipStream_t st) {
+  if (H.keys.n < 1 || H.keys.n > ORION_MAXHOIST || !hoist::in_registers(H.beta)) return -1;
+  if (D.ncomp < H.beta || D.nlimb != out.nlimb || D.nbatch != out.nbatch || own.nbatch != out.nbatch ||
+      add.nbatch != out.nbatch || own.nlimb > out.nlimb || add.nlimb > out.nlimb || out.ncomp != 2 || (N & 1))
+    return -1;
+  const int rows = out.nlimb * out.nbatch;
+  if (rows == 0) return 0;
+  if (hoist::digit_slots(H.beta) == 4)
+    hipLaunchKernelGGL(ks_mac_hoisted_kernel<4>, ew_grid(N, rows), dim3(256), 0, st, out, D, own, add, H, tb, N);
+  else
+    hipLaunchKernelGGL(ks_mac_hoisted_kernel<ORION_HOIST_MAXBETA>, ew_grid(N, rows), dim3(256), 0, st, out, D, own,
+                       add, H, tb, N);
   return 0;
 }
 

@@ -52,6 +52,8 @@ int orion_launch_modup_all(const LimbSet& D, const LimbSet& in, const BasisExtTa
                            int nqp, const DeviceTables* tb, int N, hipStream_t st);
 int orion_launch_ks_mac(const LimbSet& out, const LimbSet& D, const LimbSet& own, const MacGroups& G, int ngroup,
                         int beta, const DeviceTables* tb, int N, hipStream_t st);
+int orion_launch_ks_mac_hoisted(const LimbSet& out, const LimbSet& D, const LimbSet& own, const LimbSet& add,
+                                const MacHoist& H, const DeviceTables* tb, int N, hipStream_t st);
 int orion_launch_automorph(const LimbSet& o, const LimbSet& a, const u32* idx, const DeviceTables* tb, int N,
                            int accumulate, hipStream_t st);
 int orion_launch_lt_bsgs(const LimbSet& t0, const LimbSet& t1, const LimbSet& D, const LimbSet& ct,

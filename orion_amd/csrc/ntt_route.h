@@ -289,6 +289,23 @@ inline LtRoute lt_route(const NttEnv& e, const NttTuning& t, int B, int level, i
   return r;
 }
 
+// hoisted rotations of one ciphertext (rotate_hoisted, rotate_sum): the one
+// decomposition of c1, each output's ModDown with its automorphism, and the
+// sum's one ModDown.  sum_rows: the sum has a rotating term, so lt_giant
+// produces the accumulator and may store through the rows pass
+struct HoistRoute {
+  DecomposeRoute dec;
+  ModDownRoute out_md;  // rotate_hoisted: per output, the automorphism in its store where the kernel scatters
+  ModDownRoute sum_md;  // rotate_sum; sum_md.inv.rows_stored: lt_giant stores through the rows pass
+};
+inline HoistRoute hoist_route(const NttEnv& e, const NttTuning& t, int B, int level, bool sum_rows) {
+  HoistRoute r;
+  r.dec = decompose_route(e, t, 1, B, level);
+  r.out_md = moddown_route(e, t, 2, B, level, 1, false);
+  r.sum_md = moddown_route(e, t, 2, B, level, 0, false, sum_rows);
+  return r;
+}
+
 // rescale by the last limb (rescale_inplace): the INTT of limb `level`, then
 // the prep + NTT + (c - .) q_level^-1 of the others, in place
 inline InvFwdRoute rescale_route(const NttEnv& e, const NttTuning& t, int nc, int B, int level) {
