@@ -328,6 +328,247 @@ class SchemeCache:
         return self.val
 
 
+# ---- accumulator maxima (test_planted_mac.py, test_gpu_mac_planted.py) ----
+# every path switch of the MAC kernels (bar_k <= 48, <= 52, <= 60) has a limb on
+# each side, and every full gadget digit's product exceeds 2^61
+EDGE = dict(logn=13, logq=[60, 48, 49, 52, 53, 40, 40, 40], logp=[61, 61])
+EDGE_BITS = [60, 48, 49, 52, 54, 40, 41, 41, 61, 61]  # what gen_moduli makes of it
+WIDE = dict(logn=13, logq=[60] + [40] * 9, logp=[61])           # K = 1: beta = level + 1, 10 at the top
+LAT = dict(logn=15, logq=[60, 40, 40, 40, 40, 40], logp=[60, 60])  # ModDown on the fused latency kernels
+WIDE16 = dict(logn=15, logq=[60] + [40] * 15, logp=[61])  # K = 1, beta = 16 (test_one_prime_gadget_wide_fused_mac)
+MASK_SEED = 20261  # the positions M of the maximal key words and diagonals
+MAC_CHAINS = {"edge": EDGE, "wide": WIDE, "lat": LAT, "wide16": WIDE16}
+# (chain, level) of every planted key switch: beta = 4, 3, 3 (a single 54-bit last digit); 8, 9; 3; 16
+MAC_DIGIT_CASES = [("edge", 7), ("edge", 5), ("edge", 4), ("wide", 7), ("wide", 8), ("lat", 5), ("wide16", 15)]
+# the planted linear transforms (LogBabyStepGiantStepRatio 1): N1 = 8 with babies 1..7 under 4 giants; N1 = 16
+# with babies 1..15 under giant 0 and two babies under 7 more
+LT_IDX = {"lt8": [8 * g + s for g in range(4) for s in range(1, 8)],
+          "lt16": list(range(1, 16)) + [16 * g + s for g in range(1, 8) for s in (1, 15)]}
+
+
+def expected_digits(orc, level, target):
+    """how many gadget digits of max_digit_ct(orc, level, target) are t - 1 on
+    limb `target`: all beta, but for a last digit of a single prime narrower
+    than t (its centred value is (t - 1) mod s); with K = 1 every digit is -1"""
+    limbs = digit_limbs(level, orc.K)
+    last = limbs[-1]
+    narrow = orc.K > 1 and len(last) == 1 and target not in last and orc.moduli[last[0]] < orc.moduli[target]
+    return len(limbs) - int(narrow)
+
+
+def mform(x, q):
+    """the Montgomery form x 2^64 mod q of the wire format's coefficients (a
+    scalar as a Python int, a row as uint64 [N])"""
+    if np.ndim(x) == 0:
+        return (int(x) << 64) % q
+    return np.array([(int(v) << 64) % q for v in x], dtype=np.uint64)
+
+
+def neg_pinv_rows(orc, level):
+    """-P^-1 mod q_j, j <= level: a c0 of these constant rows makes the P c0
+    addend of a key switch q_j - 1"""
+    P = 1
+    for k in range(orc.K):
+        P *= orc.moduli[orc.L + k]
+    return [(-pow(P, -1, orc.moduli[j])) % orc.moduli[j] for j in range(level + 1)]
+
+
+def max_digit_ct(orc, level, target, c0=None):
+    """A ciphertext image [2][level+1][N] whose c1 is the NTT of the constant
+    polynomial v X^0, v = moduli[target] - 1 = t - 1: limb j is the constant
+    row (t - 1) mod q_j.  Every gadget digit whose modulus product exceeds
+    t - 1 extends to t - 1 on limb `target` (an index into orc.moduli) at every
+    NTT position, and the own digit reads t - 1 directly.  K = 1 (centred
+    digits): v = -1, all rows q_j - 1, so every digit is t - 1 on every limb at
+    once and `target` says nothing.  c0: a constant per limb (a list), a
+    [level+1][N] array, or None for 0."""
+    out = np.zeros((2, level + 1, orc.N), dtype=np.uint64)
+    v = -1 if orc.K == 1 else orc.moduli[target] - 1
+    for j in range(level + 1):
+        out[1, j, :] = v % orc.moduli[j]
+    if c0 is not None:
+        for j in range(level + 1):
+            out[0, j, :] = c0[j]
+    return out
+
+
+def digits_at_max(orc, level, target, c1):
+    """how many of the beta gadget digit words of c1 [level+1][N] on limb
+    `target` (an index into orc.moduli) are t - 1 at every NTT position, by
+    the oracle's intt, modup_digit and ntt alone"""
+    t, cnt = orc.moduli[target], 0
+    for limbs in digit_limbs(level, orc.K):
+        if target in limbs:
+            row = c1[target]
+        else:
+            src = np.stack([orc.intt(j, c1[j]) for j in limbs])
+            row = orc.ntt(target, orc.modup_digit(src, limbs, [target])[0])
+        cnt += bool(np.all(row == t - 1))
+    return cnt
+
+
+def max_mask(N, seed=MASK_SEED):
+    """M: a seeded random half of the N positions, as a bool row"""
+    return np.random.default_rng(seed).random(N) < 0.5
+
+
+def key_mask(orc, M, g):
+    """the positions a key of Galois element g is maximal on, so that the
+    products it enters meet M after the automorphism: automorphism_ntt(key_mask)
+    = M (sigma_g reads position idx_g[n] for output n)"""
+    ginv = pow(int(g), -1, 2 * orc.N)
+    return orc.automorphism_ntt(M.astype(np.uint64)[None], ginv)[0].astype(bool)
+
+
+def max_key(base, moduli, mask):
+    """the "max key": q_m - 1 on `mask` for every digit, component and modulus
+    m of base [dnum][2][L+K][N], base's own words on the rest"""
+    out = base.copy()
+    for m, q in enumerate(moduli):
+        out[:, :, m, mask] = q - 1
+    return out
+
+
+def share_at_max(orc, masks):
+    """the share of output positions where every key of masks {g: key mask}
+    is maximal once its product is read through sigma_g"""
+    hit = np.ones(orc.N, dtype=bool)
+    for g, mk in masks.items():
+        hit &= orc.automorphism_ntt(mk.astype(np.uint64)[None], g)[0].astype(bool)
+    return float(hit.mean())
+
+
+def load_galois_key_words(lib, orc, g, words, mask=None):
+    """Overwrites the polynomial words of GenerateAndSerializeRotationKey(g)'s
+    blob (the layout of test_wire_format_rotation_key_and_diagonals: 4 header
+    words; per digit 2 words and 2 components; per component the Q poly -- a
+    word L, then per limb a word N and N coefficients -- and the P poly
+    likewise) with words[d][c][m] (a residue, or a row [N] of them, per digit,
+    component and modulus; written in the wire's Montgomery form), on the
+    positions of `mask` only where one is given (the generated key's own words
+    stay on the rest), loads it, and returns the key as the oracle takes it,
+    checked against the library's."""
+    N, L, K = orc.N, orc.L, orc.K
+    blob, _ = lib.GenerateAndSerializeRotationKey(g)
+    w = blob.view(np.uint64)
+    comp = 2 + (L + K) * (1 + N)
+    assert list(w[:4]) == [g, 2 * N, 0, orc.dnum] and len(w) == 4 + orc.dnum * (2 + 2 * comp)
+    own = None
+    if mask is not None:
+        lib.LoadRotationKey(blob, g)
+        own = lib.export_galois_key(g)
+    want = np.zeros((orc.dnum, 2, L + K, N), dtype=np.uint64)
+    for d in range(orc.dnum):
+        for c in range(2):
+            base = 4 + d * (2 + 2 * comp) + 2 + c * comp
+            assert w[base] == L and w[base + 1 + L * (1 + N)] == K
+            for m in range(L + K):
+                off = base + 1 + m * (1 + N) + (1 if m >= L else 0)
+                assert w[off] == N
+                want[d, c, m] = words[d][c][m]
+                wire = mform(words[d][c][m], orc.moduli[m])
+                if mask is None:
+                    w[off + 1:off + 1 + N] = wire
+                else:
+                    w[off + 1:off + 1 + N][mask] = wire if np.ndim(wire) == 0 else wire[mask]
+    lib.LoadRotationKey(blob, g)
+    tl = lib.GetGaloisKeyLevel(g)  # (a key hinted by a linear transform is cut to its level)
+    if mask is not None:
+        want = np.where(mask, want, own)
+    want[:, :, tl + 1:L] = 0
+    want[(tl + 1 + K - 1) // K:] = 0
+    assert np.array_equal(lib.export_galois_key(g), want)
+    return want
+
+
+def load_unit_galois_key(lib, orc, g):
+    """the Galois key of g whose only non-zero entry is 1 (digit 0, component
+    0), through load_galois_key_words"""
+    words = [[[int((d, c) == (0, 0))] * (orc.L + orc.K) for c in range(2)] for d in range(orc.dnum)]
+    unit = load_galois_key_words(lib, orc, g, words)
+    tl = lib.GetGaloisKeyLevel(g)
+    ref = np.zeros((orc.dnum, 2, orc.L + orc.K, orc.N), dtype=np.uint64)
+    ref[0, 0, :tl + 1] = 1
+    ref[0, 0, orc.L:] = 1
+    assert np.array_equal(unit, ref)
+    return unit
+
+
+def load_max_galois_key(lib, orc, g, M):
+    """the max key of g: q_m - 1 on key_mask(M, g) in every digit, component
+    and modulus, the generated key elsewhere"""
+    words = [[[q - 1 for q in orc.moduli] for _ in range(2)] for _ in range(orc.dnum)]
+    return load_galois_key_words(lib, orc, g, words, mask=key_mask(orc, M, g))
+
+
+def plant_relin_key(lib, torch, words):
+    """Replaces the relinearisation key by words [dnum][2][L+K][N] through the
+    key bundle (ExportKeyBundle into a device uint8 tensor, the words written
+    over its rlk section, ImportKeyBundle): the bundle is a header of 9 words
+    and 2 per Galois key, padded to 256 bytes, then pk [2][L+K][N], then rlk,
+    as raw device words.  Checks export_relin_key() afterwards."""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    assert words.shape == lib._evk_shape()
+    n = lib.KeyBundleBytes(0)
+    buf = torch.empty(n, dtype=torch.uint8, device="cuda")
+    assert lib.lib.ExportKeyBundle(buf.data_ptr(), 0) == 0, lib.lib.OrionHipLastError()
+    lib.OrionHipSynchronize()
+    hdr = buf[:72].cpu().numpy().view(np.uint64)
+    assert hdr[3] == 1 and (hdr[5], hdr[6]) == (lib.L, lib.K)  # a relinearisation key, this chain
+    off = ((9 + 2 * int(hdr[1])) * 8 + 255) // 256 * 256 + 2 * (lib.L + lib.K) * lib.N * 8
+    assert off + words.nbytes <= n
+    buf[off:off + words.nbytes] = torch.from_numpy(words.view(np.uint8).reshape(-1)).to("cuda")
+    torch.cuda.synchronize()
+    assert lib.lib.ImportKeyBundle(buf.data_ptr(), n) == 0, lib.lib.OrionHipLastError()
+    assert np.array_equal(lib.export_relin_key(), words)
+
+
+def qp_blob(orc, level, rows):
+    """ringqp.Poly wire bytes (Q at `level`, then P) of rows[m]: a wire word
+    repeated N times, or a row [N] of them"""
+    words = []
+    for mods in (list(range(level + 1)), [orc.L + k for k in range(orc.K)]):
+        words.append(np.array([len(mods)], dtype=np.uint64))
+        for m in mods:
+            words.append(np.array([orc.N], dtype=np.uint64))
+            words.append(np.broadcast_to(np.asarray(rows[m], dtype=np.uint64), (orc.N,)))
+    return np.concatenate(words).view(np.uint8)
+
+
+def sum_expected(orc, x, gels, keys, level, memo=None):
+    """the header's definition of OrionHipRotateSum on x [B][2][level+1][N]:
+    gels the Galois element of every amount (1: the identity), keys {g: key}.
+    memo: a dict that keeps the rotated gadget products per (image, g) between
+    calls on the same x and keys."""
+    nq, K, N = level + 1, orc.K, orc.N
+    P = 1
+    for k in range(K):
+        P *= orc.moduli[orc.L + k]
+    qp = orc.qp_mods(level)
+    q = np.array([orc.moduli[m] for m in qp], dtype=np.uint64)[:, None]
+    pq = np.zeros((nq, N), dtype=np.uint64)
+    for j in range(nq):
+        pq[j, :] = P % orc.moduli[j]
+    zeros = np.zeros((K, N), dtype=np.uint64)
+    memo = {} if memo is None else memo
+    out = np.zeros((x.shape[0], 2, nq, N), dtype=np.uint64)
+    for b in range(x.shape[0]):
+        pc = [np.concatenate([orc.mul_coeffs(x[b, c, :nq], pq, list(range(nq))), zeros]) for c in range(2)]
+        acc = [np.zeros((nq + K, N), dtype=np.uint64) for _ in range(2)]
+        for g in gels:
+            if g == 1:
+                r = pc
+            else:
+                if (b, g) not in memo:
+                    u0, u1 = orc.gadget_product_lazy(x[b, 1, :nq], keys[g], level)
+                    u0 = (u0 % q + pc[0]) % q  # residues are below 2^61: a sum of two fits a uint64
+                    memo[b, g] = [orc.automorphism_ntt(u0, g), orc.automorphism_ntt(u1 % q, g)]
+                r = memo[b, g]
+            acc = [(acc[c] + r[c]) % q for c in range(2)]
+        out[b] = np.stack([orc.moddown(acc[0], level), orc.moddown(acc[1], level)])
+    return out
+
+
 def bootstrap_keys(lib, ns):
     """The keys of the bootstrapper for `ns` slots (relinearisation, Galois,
     EvkDenseToSparse, EvkSparseToDense): with the input ciphertext, the only

@@ -15,7 +15,7 @@ images 0 and B - 1 (the other images are copies of those two)."""
 import numpy as np
 import pytest
 
-from tests.helpers import PLANT_CHAINS, SchemeCache, plant_digit_values
+from tests.helpers import PLANT_CHAINS, SchemeCache, load_unit_galois_key, mform, plant_digit_values, qp_blob
 
 pytestmark = pytest.mark.gpu
 
@@ -176,40 +176,6 @@ def test_modup_planted_ntt_prologue(torch_cuda, oracle_mod, monkeypatch, env, B,
         assert prof["basis_ext"] > 0 and prof.get("ntt_bext", 0) == 0, prof
 
 
-def mform_one(q):
-    """the Montgomery form of 1 (the wire format's coefficients)"""
-    return (1 << 64) % q
-
-
-def load_unit_galois_key(lib, orc, g):
-    """Overwrites the polynomial words of GenerateAndSerializeRotationKey(g)'s
-    blob (the layout of test_wire_format_rotation_key_and_diagonals: 4 header
-    words; per digit 2 words and 2 components; per component the Q poly -- a
-    word L, then per limb a word N and N coefficients -- and the P poly
-    likewise) with 1 in digit 0, component 0 and 0 elsewhere, loads it, and
-    returns the key as the oracle takes it, checked against the library's."""
-    N, L, K = orc.N, orc.L, orc.K
-    blob, _ = lib.GenerateAndSerializeRotationKey(g)
-    w = blob.view(np.uint64)
-    comp = 2 + (L + K) * (1 + N)
-    assert list(w[:4]) == [g, 2 * N, 0, orc.dnum] and len(w) == 4 + orc.dnum * (2 + 2 * comp)
-    for d in range(orc.dnum):
-        for c in range(2):
-            base = 4 + d * (2 + 2 * comp) + 2 + c * comp
-            assert w[base] == L and w[base + 1 + L * (1 + N)] == K
-            for m in range(L + K):
-                off = base + 1 + m * (1 + N) + (1 if m >= L else 0)
-                assert w[off] == N
-                w[off + 1:off + 1 + N] = mform_one(orc.moduli[m]) if (d, c) == (0, 0) else 0
-    lib.LoadRotationKey(blob, g)
-    tl = lib.GetGaloisKeyLevel(g)  # (a key hinted by a linear transform is cut to its level)
-    unit = np.zeros((orc.dnum, 2, L + K, N), dtype=np.uint64)
-    unit[0, 0, :tl + 1] = 1
-    unit[0, 0, L:] = 1
-    assert np.array_equal(lib.export_galois_key(g), unit)
-    return unit
-
-
 def check_moddown(lib, orc, level, B, rng):
     x = planted_cts(rng, orc, level, B)
     g = int(lib.GaloisElement(ROT_UNIT))
@@ -256,17 +222,6 @@ def test_moddown_planted_ntt_prologue(torch_cuda, oracle_mod):
     assert prof["ntt_bext"] > 0 and prof.get("basis_ext", 0) == 0, prof
 
 
-def qp_blob(orc, level, rows):
-    """ringqp.Poly wire bytes (Q at `level`, then P) of rows[m] repeated N times"""
-    words = []
-    for mods in (list(range(level + 1)), [orc.L + k for k in range(orc.K)]):
-        words.append(np.array([len(mods)], dtype=np.uint64))
-        for m in mods:
-            words.append(np.array([orc.N], dtype=np.uint64))
-            words.append(np.full(orc.N, rows[m], dtype=np.uint64))
-    return np.concatenate(words).view(np.uint8)
-
-
 @pytest.mark.parametrize("level,B", [(5, 1), (5, 4), (1, 1), (1, 4)])
 def test_moddown_rescale_planted(torch_cuda, oracle_mod, monkeypatch, level, B):
     """basis_ext_rescale_kernel<2> on planted sources (SMALL, N = 2^13): a
@@ -300,7 +255,7 @@ def test_moddown_rescale_planted(torch_cuda, oracle_mod, monkeypatch, level, B):
         assert gels
         gkeys = {g: load_unit_galois_key(lib, orc, g) for g in gels}
         assert all(lib.GetGaloisKeyLevel(g) == level for g in gels)
-        lib.LoadPlaintextDiagonal(qp_blob(orc, level, [mform_one(q) for q in orc.moduli]), lt, 1)
+        lib.LoadPlaintextDiagonal(qp_blob(orc, level, [mform(1, q) for q in orc.moduli]), lt, 1)
         pts = [lib.export_lt_diagonal(lt, 1, level)]
         assert np.all(pts[0] == 1)
         ct = lib.import_ciphertext(x, 2.0 ** 40)

@@ -14,14 +14,12 @@ import threading
 import numpy as np
 import pytest
 
-from tests.helpers import SMALL, SchemeCache, rand_ct
+from tests.helpers import LAT, SMALL, WIDE, SchemeCache, rand_ct, sum_expected
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCALE = 2.0 ** 40
-WIDE = dict(logn=13, logq=[60] + [40] * 9, logp=[61])           # K = 1: beta = level + 1, 10 at the top
-LAT = dict(logn=15, logq=[60, 40, 40, 40, 40, 40], logp=[60, 60])  # ModDown on the fused latency kernels
 
 
 def _define(name):
@@ -129,37 +127,6 @@ def check_hoisted(env, x, amounts, level, rotate_new=False):
     delete(lib, outs + [ct])
 
 
-def sum_expected(env, x, amounts, level):
-    """the header's definition of OrionHipRotateSum on x [B][2][level+1][N]"""
-    lib, orc = env.lib, env.orc
-    nq, K, N = level + 1, lib.K, lib.N
-    qp = orc.qp_mods(level)
-    q = np.array([env.mods[m] for m in qp], dtype=np.uint64)[:, None]
-    pq = np.zeros((nq, N), dtype=np.uint64)
-    for j in range(nq):
-        pq[j, :] = env.P % env.mods[j]
-    zeros = np.zeros((K, N), dtype=np.uint64)
-    keys = env.keys(amounts)
-    out = np.zeros((x.shape[0], 2, nq, N), dtype=np.uint64)
-    for b in range(x.shape[0]):
-        pc = [np.concatenate([orc.mul_coeffs(x[b, c, :nq], pq, list(range(nq))), zeros]) for c in range(2)]
-        acc = [np.zeros((nq + K, N), dtype=np.uint64) for _ in range(2)]
-        memo = {}
-        for k in amounts:
-            g = env.g(k)
-            if g == 1:
-                r = pc
-            else:
-                if g not in memo:
-                    u0, u1 = orc.gadget_product_lazy(x[b, 1, :nq], keys[g], level)
-                    u0 = (u0 % q + pc[0]) % q  # residues are below 2^61: a sum of two fits a uint64
-                    memo[g] = [orc.automorphism_ntt(u0, g), orc.automorphism_ntt(u1 % q, g)]
-                r = memo[g]
-            acc = [(acc[c] + r[c]) % q for c in range(2)]
-        out[b] = np.stack([orc.moddown(acc[0], level), orc.moddown(acc[1], level)])
-    return out
-
-
 def check_sum(env, x, amounts, level):
     lib = env.lib
     ct = lib.import_ciphertext(x, SCALE)
@@ -167,7 +134,8 @@ def check_sum(env, x, amounts, level):
     assert lib.GetCiphertextLevel(h) == level and lib.GetCiphertextBatch(h) == x.shape[0]
     assert lib.GetCiphertextScaleF(h) == SCALE
     got = lib.export_ciphertext(h)
-    assert np.array_equal(got, sum_expected(env, x, amounts, level)), (amounts, level, x.shape[0])
+    ref = sum_expected(env.orc, x, [env.g(k) for k in amounts], env.keys(amounts), level)
+    assert np.array_equal(got, ref), (amounts, level, x.shape[0])
     delete(lib, [ct, h])
     return got
 
