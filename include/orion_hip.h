@@ -488,6 +488,91 @@ int OrionHipPackComplex(int a, int b);
 int OrionHipUnpackComplex(int ct, int *out2);
 int OrionHipBootstrapPacked(int ct, int slots);
 
+/* Slot-packed bootstrapping: N / (2 slots) sparse images per circuit run.
+ *
+ * An image with n = slots slots, projected onto Z[X^g] with g = N / (2 n),
+ * occupies only the coefficients at multiples of g.  So g such images share
+ * one ciphertext as sum_i X^i image_i, one full-slot bootstrap refreshes all
+ * of them, and multiplying by X^-i and summing over the rotations by n 2^s
+ * (the automorphisms that fix Z[X^g]) pulls image i out again.
+ *
+ * Let M_k be the NTT of X^k over the Q limbs of the calling context's chain,
+ * k taken mod 2N with X^(N + k) = -X^k (coefficient j of limb l is
+ * psi_l^(k (2 brv(j) + 1))), and L - 1 the residual top level.  All arithmetic
+ * below is limb by limb mod q_l, on both components; o is the elementwise
+ * product.
+ *
+ *   OrionHipPackMonomials(ct, g): a batch of B images becomes a batch of
+ *       h = ceil(B / g): out_k = sum over i with k + i h < B of
+ *       M_i o ct_(k + i h).  Image k + i h rides in group k at X^i (the
+ *       stride-h convention of OrionHipBootstrapPacked).  ct's level and
+ *       scale; 1 <= g <= N; one kernel launch.
+ *   OrionHipUnpackMonomials(ct, g, B): a batch of h = ceil(B / g) images
+ *       (anything else is an error) becomes a batch of B:
+ *       out_(k + i h) = M_-i o ct_k.  ct's level and scale; one kernel launch
+ *       that reads each source row once and writes its (at most g) images.
+ *   OrionHipSlotTraceNew(ct, slots, mean): t_0 = ct (mean = 0) or
+ *       (g^-1 mod q_l) o ct (mean = 1: scaled before the rotations; after them
+ *       the scaling would multiply the key-switch noise), then
+ *       t_(s+1) = t_s + Rotate(t_s, n 2^s) for s = 0 .. log2(g) - 1; the result
+ *       is t at ct's level, scale and batch, bit-equal to that loop of
+ *       RotateNew and AddCiphertextNew.  Slot k of the result holds the sum
+ *       (mean = 0) or the mean (mean = 1) of the g slots k + n j; the mean is
+ *       the exact projection onto Z[X^g].  slots = N / 2 returns a copy.  With
+ *       the secret key every Galois key is made at first use, as Rotate does;
+ *       without it the keys must have been loaded, otherwise the call fails as
+ *       a rotation without its key does.  Every key is made or checked at
+ *       level L - 1 before anything is allocated.
+ *   OrionHipBootstrapMany(ct, slots): a batch of B images with `slots` slots
+ *       refreshed by the FULL-SLOT circuit run at batch h = ceil(B / g).  Only
+ *       limb 0 of ct is read, as in Bootstrap.  With x = ct's limb-0 ciphertext:
+ *         u = OrionHipSlotTraceNew(x, slots, 1)      at level 0
+ *         p = OrionHipPackMonomials(u, g)            batch h
+ *         r = Bootstrap(p, N / 2)                    ScaleDown and circuit unchanged
+ *         w = OrionHipUnpackMonomials(r, g, B)       at level L - 1
+ *         out = OrionHipSlotTraceNew(w, slots, 0)
+ *       The result is bit-equal to that composition after CloneCiphertext and
+ *       ModDropCiphertext to level 0: level L - 1, batch B, the scale
+ *       Bootstrap(., N / 2) gives for the input scale (which is the sparse
+ *       bootstrapper's).  It holds the values Bootstrap(ct, slots) returns:
+ *       slot k = sum_j in[(k mod n) + n j], replicated; the g^-1 of the input
+ *       trace and the post-scale g cancel against the output trace, so the call
+ *       scales nothing itself.  slots = N / 2 is Bootstrap(ct, N / 2) bit for
+ *       bit.  It needs the N / 2 bootstrapper (NewBootstrapper(logPs, N / 2));
+ *       one for `slots` is not needed.  From a pipeline thread it runs on the
+ *       scheme's bootstrapper, as Bootstrap.
+ *
+ * Where the call pays: the circuit work falls from B sparse runs to
+ * ceil(B / g) full-slot ones, against log2(g) key switches on B images at
+ * level 0 and again at level L - 1 that Bootstrap does not run there.  The
+ * gain grows with g and with B.  Measured on one MI355X at B = 8, N = 2^16,
+ * P = [61] x 8 (time of Bootstrap(ct, slots) / time of this call): 1.49 at
+ * 16384 slots (g = 2), 2.41 at 8192, 3.28 at 4096; at N = 2^13, where the
+ * circuit is latency-bound, 1.05, 1.26 and 1.39.  It was slower at no point
+ * measured (tools/btp_many_ab.py).
+ *
+ * It composes with complex packing (g divides N / 2, so I commutes with every
+ * step): OrionHipPackComplex, OrionHipBootstrapMany, OrionHipUnpackComplex
+ * refreshes 2 g real images per circuit run.
+ *
+ * All four: the results are new handles of the calling thread's context; a
+ * pending deferred op runs first; an operand of another context is read like
+ * any foreign operand.  After one warm call (which makes the factor rows M_1,
+ * M_-1 and the Galois keys) the first three may be captured into a graph;
+ * OrionHipBootstrapMany, like Bootstrap, may not.
+ *
+ * Errors: -1 and OrionHipLastError for an unknown handle, g outside [1, N],
+ * slots that is no power of two in [2, N / 2], a batch that is not
+ * ceil(B / g), no full-slot bootstrapper (the message names N / 2 and
+ * NewBootstrapper), a missing Galois key without the secret (the message names
+ * the element), a ConjugateInvariant scheme, a poisoned source (its poison
+ * message) and, for OrionHipBootstrapMany, an open graph capture.  A failed
+ * call allocates no handle. */
+int OrionHipPackMonomials(int ct, int g);
+int OrionHipUnpackMonomials(int ct, int g, int B);
+int OrionHipSlotTraceNew(int ct, int slots, int mean);
+int OrionHipBootstrapMany(int ct, int slots);
+
 /* GPU encoder with device-resident slots (e.g. a torch tensor's data_ptr):
  * dvalues [batch][lenPerImage] float32; DecodeDevice writes the real parts of
  * all slots, [batch][N/2] float64, to device memory (asynchronous);
@@ -587,7 +672,8 @@ int OrionHipImportBootstrapKey(int slots, const void *dptr, unsigned long bytes)
 /* kernel timing with HIP events on the library stream; enable: 0 = off,
  * 1 = every category, otherwise a bit mask of categories (bit 0 ntt_fwd,
  * 1 ntt_inv, 2 elementwise, 3 basis_ext, 4 ks_mac, 5 automorph, 6 tensor,
- * 7 rescale_prep, 8 lt_bsgs, 9 lt_giant) */
+ * 7 rescale_prep, 8 lt_bsgs, 9 lt_giant, 10 ntt_bext, 11 mono_pack,
+ * 12 mono_unpack) */
 void OrionHipProfile(int enable);
 /* fills up to max entries: name (32 chars each), launches, total ms, algorithmic
  * bytes (NTT: 16 N per limb-transform + 8 N per epilogue operand or addend read,

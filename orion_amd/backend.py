@@ -180,6 +180,10 @@ SIGNATURES = {
     "OrionHipPackComplex": ([c_int, c_int], c_int),
     "OrionHipUnpackComplex": ([c_int, P(c_int)], c_int),
     "OrionHipBootstrapPacked": ([c_int, c_int], c_int),
+    "OrionHipPackMonomials": ([c_int, c_int], c_int),
+    "OrionHipUnpackMonomials": ([c_int, c_int, c_int], c_int),
+    "OrionHipSlotTraceNew": ([c_int, c_int, c_int], c_int),
+    "OrionHipBootstrapMany": ([c_int, c_int], c_int),
     "ImportCiphertext": ([P(c_ulong), c_int, c_int, c_double], c_int),
     "ExportCiphertext": ([c_int, P(c_ulong), c_ulong], c_int),
     "ImportPlaintext": ([P(c_ulong), c_int, c_int, c_double], c_int),
@@ -623,6 +627,32 @@ class HipLibrary:
         images at twice Bootstrap's scale."""
         self.lib.OrionHipClearError()
         return self._chk(self.lib.OrionHipBootstrapPacked(int(ct), int(slots)), "OrionHipBootstrapPacked")
+
+    # ---- slot-packed bootstrapping (include/orion_hip.h) ------------------
+    def pack_monomials(self, ct, g):
+        """A batch of B images as ceil(B / g) groups, image k + i h in group k
+        at X^i (OrionHipPackMonomials): a new handle at ct's level and scale."""
+        self.lib.OrionHipClearError()
+        return self._chk(self.lib.OrionHipPackMonomials(int(ct), int(g)), "OrionHipPackMonomials")
+
+    def unpack_monomials(self, ct, g, batch):
+        """The `batch` images X^-i o group k of a batch of ceil(batch / g)
+        groups (OrionHipUnpackMonomials), before the trace that isolates them."""
+        self.lib.OrionHipClearError()
+        return self._chk(self.lib.OrionHipUnpackMonomials(int(ct), int(g), int(batch)), "OrionHipUnpackMonomials")
+
+    def slot_trace_new(self, ct, slots, mean=False):
+        """The sum (mean: the mean) of the N / (2 slots) slots at distance
+        `slots`, in every slot, as a new handle (OrionHipSlotTraceNew)."""
+        self.lib.OrionHipClearError()
+        return self._chk(self.lib.OrionHipSlotTraceNew(int(ct), int(slots), 1 if mean else 0), "OrionHipSlotTraceNew")
+
+    def bootstrap_many(self, ct, slots):
+        """Bootstrap(ct, slots) of a batch of B sparse images on the full-slot
+        circuit at batch ceil(B / g), g = N / (2 slots)
+        (OrionHipBootstrapMany): needs the N / 2 bootstrapper only."""
+        self.lib.OrionHipClearError()
+        return self._chk(self.lib.OrionHipBootstrapMany(int(ct), int(slots)), "OrionHipBootstrapMany")
 
     # Device-pointer calls run asynchronously on the library stream, which
     # torch does not know about: order them against the tensor's stream both

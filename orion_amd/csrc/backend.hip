@@ -595,10 +595,12 @@ struct ProfRec {
   double bytes, strict;
 };
 static const char* kProfNames[] = {"ntt_fwd", "ntt_inv", "elementwise", "basis_ext", "ks_mac", "automorph",
-                                   "tensor", "rescale_prep", "lt_bsgs", "lt_giant", "ntt_bext"};
+                                   "tensor", "rescale_prep", "lt_bsgs", "lt_giant", "ntt_bext",
+                                   "mono_pack", "mono_unpack"};
 // ntt_bext: forward NTTs whose prologue forms the extended limb (NTT_PRO_BEXT),
 // priced (ns + 1) 8 N per limb-transform (+ 8 N for a subtract-and-scale epilogue)
-enum { P_NTT_FWD = 0, P_NTT_INV, P_EW, P_BEXT, P_MAC, P_AUT, P_TENSOR, P_RSPREP, P_LTMAC, P_LTGIANT, P_NTT_BEXT, P_NCAT };
+enum { P_NTT_FWD = 0, P_NTT_INV, P_EW, P_BEXT, P_MAC, P_AUT, P_TENSOR, P_RSPREP, P_LTMAC, P_LTGIANT, P_NTT_BEXT,
+       P_MONOPACK, P_MONOUNPACK, P_NCAT };
 
 // wall-clock intervals of the profiled launches of every context (peer
 // pipelines run concurrently), relative to one reference event
@@ -2394,6 +2396,124 @@ struct Context {
     return {std::move(re), std::move(im)};
   }
 
+  // -- monomial packing and the slot trace (orion_hip.h Part 2) ---------------
+  // An image with n slots, projected onto Z[X^g] (g = N / (2 n)), occupies the
+  // coefficients at multiples of g only, so g of them share one ciphertext as
+  // sum_i X^i image_i; multiplying by X^-i and summing over the automorphisms
+  // that fix Z[X^g] (slot_trace) pulls image i out again.  M_1 and M_-1, the
+  // NTTs of X and of X^-1 = -X^(N-1) on every Q limb ([2][L][N], made at first
+  // use by the forward NTT of the unit vectors, kept): the kernels form M_(+-i)
+  // as running products (kernels.hip mono_pack_kernel).
+  Poly mono;
+  void check_mono_ring() const {
+    if (ci)
+      throw std::runtime_error("monomial packing needs the Standard ring (a ConjugateInvariant ring has no X^i "
+                               "that the slot trace separates)");
+  }
+  void need_mono() {
+    check_mono_ring();
+    if (mono.buf) return;
+    no_capture("the monomial factor table");
+    std::vector<u64> host((size_t)2 * L * N, 0);
+    for (int j = 0; j < L; ++j) {
+      host[(size_t)j * N + 1] = 1;
+      host[((size_t)L + j) * N + (N - 1)] = mods[j] - 1;
+    }
+    Poly m = alloc(2, L, 1);
+    upload(m, host);
+    ntt(lsq(m, 0, 2, L - 1), false);
+    mono = m;
+  }
+  // ceil(B / g) for any B, g >= 1 (no B + g - 1: B may be any int)
+  static long long mono_groups(long long B, long long g) { return (B + g - 1) / g; }
+  void check_mono_g(int g) const {
+    check_mono_ring();
+    if (g < 1 || g > N)
+      throw std::runtime_error("monomial packing: g = " + std::to_string(g) + " is out of range [1, " +
+                               std::to_string(N) + "]");
+  }
+  // o_k = sum_i M_i a_(k + i h) on the limbs 0..level; one launch.  Bytes per
+  // (comp, limb, group) row: its images and the output; per limb the factor row
+  void mono_pack_launch(const LimbSet& o, const LimbSet& a, int level, int g) {
+    Scope sc(this, P_MONOPACK, 8.0 * N * (o.nlimb * (o.ncomp * (double)(a.nbatch + o.nbatch) + 1)));
+    if (orion_launch_mono_pack(o, a, lsq(mono, 0, 1, level), g, d_tb, N, stream))
+      throw std::runtime_error("mono_pack launch failed (batch or limb count out of range)");
+  }
+  void mono_unpack_launch(const LimbSet& o, const LimbSet& x, int level, int g) {
+    Scope sc(this, P_MONOUNPACK, 8.0 * N * (x.nlimb * (x.ncomp * (double)(o.nbatch + x.nbatch) + 1)));
+    if (orion_launch_mono_unpack(o, x, lsq(mono, 1, 1, level), g, d_tb, N, stream))
+      throw std::runtime_error("mono_unpack launch failed (batch or limb count out of range)");
+  }
+  // the batch of B images as h = ceil(B / g) groups: image k + i h rides in
+  // group k at X^i.  The arguments are checked before the factor rows are made
+  Ciphertext pack_monomials(const Ciphertext& a, int g) {
+    check_mono_g(g);
+    need_mono();
+    const int level = a.level, B = a.poly.B;
+    Ciphertext o = new_ct(level, (int)mono_groups(B, g), a.scale);
+    mono_pack_launch(lsq(o.poly, 0, 2, level), lsq(a.poly, 0, 2, level), level, g);
+    return o;
+  }
+  // out_(k + i h) = M_-i a_k: B images out of h = ceil(B / g) groups
+  Ciphertext unpack_monomials(const Ciphertext& a, int g, int B) {
+    check_mono_g(g);
+    const long long need = B < 1 ? 0 : mono_groups(B, g);
+    if (B < 1 || a.poly.B != need)
+      throw std::runtime_error("cannot unpack " + std::to_string(B) + " images at g = " + std::to_string(g) +
+                               " from a batch of " + std::to_string(a.poly.B) + ": ceil(B / g) = " +
+                               std::to_string(need) + " groups are needed");
+    need_mono();
+    const int level = a.level;
+    Ciphertext o = new_ct(level, B, a.scale);
+    mono_unpack_launch(lsq(o.poly, 0, 2, level), lsq(a.poly, 0, 2, level), level, g);
+    return o;
+  }
+  // the rotation amounts ns 2^s of the trace over the g = N / (2 ns) slots at
+  // distance ns (Bootstrapper::trace_gal's order); checks the ring and ns
+  std::vector<int> slot_trace_amounts(int ns) const {
+    check_mono_ring();
+    if (ns < 2 || ns > N / 2 || (ns & (ns - 1)))
+      throw std::runtime_error("slots must be a power of two in [2, " + std::to_string(N / 2) + "]");
+    std::vector<int> ks;
+    for (int s = ns; s < N / 2; s *= 2) ks.push_back(s);
+    return ks;
+  }
+  // every Galois key of the amounts made or checked at the top level, before
+  // the caller allocates anything
+  void slot_trace_keys(const std::vector<int>& ks) {
+    for (int k : ks) {
+      const u64 gel = galois_element(k);
+      try {
+        galois_key(gel, L - 1);
+      } catch (const std::runtime_error& e) {  // Rotate's message, with the element it lacks
+        throw std::runtime_error("slot trace: galois key " + std::to_string(gel) + " (rotation by " +
+                                 std::to_string(k) + ") at level " + std::to_string(L - 1) + ": " + e.what());
+      }
+    }
+  }
+  // t = src (mean: g^-1 src, scaled before the rotations: after them it would
+  // multiply the key-switch noise), then t += Rotate(t, k) for k of ks (checked
+  // amounts whose keys exist); src: the limbs 0..level of a ciphertext's pair
+  Ciphertext slot_trace_run(const Poly& src, int level, long double scale, const std::vector<int>& ks, bool mean) {
+    Ciphertext t = new_ct(level, src.B, scale);
+    const LimbSet tl = lsq(t.poly, 0, 2, level), sl = lsq(src, 0, 2, level);
+    if (mean && !ks.empty()) {
+      const u64 g = (u64)1 << ks.size();
+      std::vector<u64> gi(level + 1);
+      for (int l = 0; l <= level; ++l) gi[l] = hm_invmod(g % mods[l], mods[l]);
+      ew1(EW_SCALE, tl, sl, &gi);
+    } else {
+      copy(tl, sl);
+    }
+    for (int k : ks) rotate_add_inplace(t, k);
+    return t;
+  }
+  Ciphertext slot_trace(const Poly& src, int level, long double scale, int ns, bool mean) {
+    const std::vector<int> ks = slot_trace_amounts(ns);
+    slot_trace_keys(ks);
+    return slot_trace_run(src, level, scale, ks, mean);
+  }
+
   // scale matching for additions (Lattigo evaluateInPlace: the lower-scale
   // operand is multiplied by the rounded integer ratio when it is > 1)
   void add_like(Ciphertext& out, const Ciphertext& a, const LimbSet& b, long double bscale, int op) {
@@ -3659,6 +3779,34 @@ struct Context {
     im.p = np ? out.poly.ptr() + (long long)h * out.poly.batch_stride() : nullptr;
     unpack_launch(re, im, lsq(r.poly, 0, 2, r.level), lsq(yc.poly, 0, 2, r.level), np);
     return out;
+  }
+  // bootstrap of a batch of B images with ns slots each as h = ceil(B / g)
+  // full-slot ones, g = N / (2 ns): the mean trace of limb 0 projects every
+  // image onto Z[X^g], image k + i h rides in group k at X^i through the
+  // full-slot bootstrapper's ScaleDown and circuit, and the unpack and the sum
+  // trace at the residual top level pull it out again.  The g^-1 of the input
+  // trace cancels against the g of the output trace, which also stands for the
+  // sparse bootstrapper's post-scale: no scaling here.  Every step is the
+  // public call's, so the bits are those of CloneCiphertext, ModDropCiphertext
+  // to level 0, OrionHipSlotTraceNew(mean), OrionHipPackMonomials, Bootstrap(N / 2),
+  // OrionHipUnpackMonomials, OrionHipSlotTraceNew.  ns = N / 2 is bootstrap.
+  Ciphertext bootstrap_many(const Ciphertext& in, int ns) {
+    const std::vector<int> ks = slot_trace_amounts(ns);  // (the ring and ns checked)
+    if (!btps.count(N / 2))
+      throw std::runtime_error("OrionHipBootstrapMany runs the full-slot circuit: no bootstrapper found for slot "
+                               "count N/2 = " + std::to_string(N / 2) + " (NewBootstrapper(logPs, " +
+                               std::to_string(N / 2) + ") makes it; one for " + std::to_string(ns) +
+                               " slots is not needed)");
+    if (ks.empty()) return bootstrap(in, ns);
+    const int g = 1 << ks.size(), B = in.poly.B;
+    slot_trace_keys(ks);  // every key, before anything is allocated
+    need_mono();
+    const Ciphertext u = slot_trace_run(in.poly, 0, in.scale, ks, true);
+    const Ciphertext p = pack_monomials(u, g);
+    const Ciphertext r = bootstrap(p, N / 2);
+    Ciphertext w = unpack_monomials(r, g, B);
+    for (int k : ks) rotate_add_inplace(w, k);  // the sum trace, on the unpacked images themselves (no copy)
+    return w;
   }
   void delete_bootstrappers() {
     if (stream) HIPCHK(hipStreamSynchronize(stream));
@@ -4932,6 +5080,32 @@ int OrionHipUnpackComplex(int ct, int* out2) {
   API_END(-1)
 }
 
+// ---- monomial packing and the slot trace (orion_hip.h; Context::pack_monomials, slot_trace) ----
+int OrionHipPackMonomials(int ct, int g) {
+  API_BEGIN
+  Context& c = ctx();
+  const Ciphertext& a = complex_operand(c, ct);
+  std::shared_ptr<Buffer> keep = a.poly.buf;  // the operand's buffer, until the launches are queued
+  return c.cts.add(c.pack_monomials(a, g));
+  API_END(-1)
+}
+int OrionHipUnpackMonomials(int ct, int g, int B) {
+  API_BEGIN
+  Context& c = ctx();
+  const Ciphertext& a = complex_operand(c, ct);
+  std::shared_ptr<Buffer> keep = a.poly.buf;
+  return c.cts.add(c.unpack_monomials(a, g, B));
+  API_END(-1)
+}
+int OrionHipSlotTraceNew(int ct, int slots, int mean) {
+  API_BEGIN
+  Context& c = ctx();
+  const Ciphertext& a = complex_operand(c, ct);
+  std::shared_ptr<Buffer> keep = a.poly.buf;
+  return c.cts.add(c.slot_trace(a.poly, a.level, a.scale, slots, mean != 0));
+  API_END(-1)
+}
+
 // ---- linear transforms ----
 void NewLinearTransformEvaluator(void) {}
 
@@ -5379,18 +5553,21 @@ void NewBootstrapper(int* logPs, int n, int slots) {
 }
 // bootstrapper.go:61-80: a new ciphertext refreshed to the residual top level,
 // at the input's scale, post-scaled by 2^(LogMaxSlots - LogSlots)
-// (packed: Context::bootstrap_packed in its place, OrionHipBootstrapPacked)
-static int bootstrap_handle(int ct, int slots, bool packed) {
+// (BTP_PACKED: Context::bootstrap_packed in its place, OrionHipBootstrapPacked;
+// BTP_MANY: Context::bootstrap_many, on the full-slot bootstrapper, OrionHipBootstrapMany)
+enum BtpKind { BTP_PLAIN, BTP_PACKED, BTP_MANY };
+static int bootstrap_handle(int ct, int slots, BtpKind kind) {
   Context& c = ctx();
   Context* s = scheme_ctx();
+  const bool packed = kind == BTP_PACKED;
   if (packed) c.need_complex();
   auto run = [&](Context& on, const Ciphertext& in) {
-    if (!packed) return on.bootstrap(in, slots);
+    if (kind == BTP_PLAIN) return on.bootstrap(in, slots);
     if (!in.poly.ptr() || in.poly.ncomp < 2)
       throw std::runtime_error("ciphertext " + std::to_string(ct) + " holds no degree-1 polynomial pair");
-    return on.bootstrap_packed(in, slots);
+    return packed ? on.bootstrap_packed(in, slots) : on.bootstrap_many(in, slots);
   };
-  if (c.btps.count(slots) || !s || s == &c) return c.cts.add(run(c, c.cts.get(ct)));
+  if (c.btps.count(kind == BTP_MANY ? c.N / 2 : slots) || !s || s == &c) return c.cts.add(run(c, c.cts.get(ct)));
   // a pipeline bootstraps with the scheme's bootstrapper (one circuit and key
   // set per process), on the scheme's stream under the scheme's lock: the
   // scheme's stream waits for the input, the result is copied into a buffer
@@ -5417,13 +5594,19 @@ static int bootstrap_handle(int ct, int slots, bool packed) {
 }
 int Bootstrap(int ct, int slots) {
   API_BEGIN
-  return bootstrap_handle(ct, slots, false);
+  return bootstrap_handle(ct, slots, BTP_PLAIN);
   API_END(-1)
 }
 // the batch refreshed two images per circuit run (orion_hip.h; Context::bootstrap_packed)
 int OrionHipBootstrapPacked(int ct, int slots) {
   API_BEGIN
-  return bootstrap_handle(ct, slots, true);
+  return bootstrap_handle(ct, slots, BTP_PACKED);
+  API_END(-1)
+}
+// the batch refreshed N / (2 slots) sparse images per full-slot circuit run (orion_hip.h; Context::bootstrap_many)
+int OrionHipBootstrapMany(int ct, int slots) {
+  API_BEGIN
+  return bootstrap_handle(ct, slots, BTP_MANY);
   API_END(-1)
 }
 void DeleteBootstrappers(void) {

@@ -42,9 +42,11 @@ constexpr Call kCalls[] = {
     {"MulScalarInt", 1, 0}, {"MulScalarIntNew", 1, 0}, {"Negate", 1, 0}, {"OrionHipConjugateNew", 1, 0},
     {"OrionHipCurrentPipeline", 1, 1},
     {"OrionHipEvaluateLinearTransformBlocks", 1, 0}, {"OrionHipGetStream", 1, 1}, {"OrionHipGraphEnd", 1, 0},
-    {"OrionHipMulRelinSum", 1, 0}, {"OrionHipPackComplex", 1, 0}, {"OrionHipPeerCount", 0, 1},
+    {"OrionHipMulRelinSum", 1, 0}, {"OrionHipPackComplex", 1, 0}, {"OrionHipPackMonomials", 1, 0},
+    {"OrionHipPeerCount", 0, 1},
     {"OrionHipPeerSelect", 0, 1}, {"OrionHipRotateAdd", 1, 0}, {"OrionHipRotateHoisted", 1, 0},
-    {"OrionHipRotateSum", 1, 0}, {"OrionHipUnpackComplex", 1, 0}, {"Rescale", 1, 1},
+    {"OrionHipRotateSum", 1, 0}, {"OrionHipSlotTraceNew", 1, 0}, {"OrionHipUnpackComplex", 1, 0},
+    {"OrionHipUnpackMonomials", 1, 0}, {"Rescale", 1, 1},
     {"RescaleNew", 1, 1},
     {"Rotate", 1, 0}, {"RotateNew", 1, 0}, {"SetCiphertextScale", 1, 0}, {"SetPlaintextScale", 1, 0},
     {"SubCiphertext", 1, 0}, {"SubCiphertextNew", 1, 0}, {"SubPlaintext", 1, 0}, {"SubPlaintextNew", 1, 0},

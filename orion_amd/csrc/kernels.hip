@@ -158,6 +158,72 @@ __global__ void __launch_bounds__(256) unpack_complex_kernel(LimbSet re, LimbSet
   *(ulonglong2*)(im.p + row_off(im, c, l, bi) + n) = make_ulonglong2(shoup_mul(d0, w, ws, q), shoup_mul(d1, w, ws, q));
 }
 
+// Monomial packing (OrionHipPackMonomials / OrionHipUnpackMonomials).  M_i =
+// NTT of X^i is the i-th power of M_1 coefficient by coefficient, so a thread
+// carries the running product f_i = f_(i-1) m of its two coefficients of m =
+// M_1 (pack) or M_-1 (unpack) and reads no table of powers.  Every product is
+// fully reduced before it is added or stored, so g is bounded by nothing.
+// Rows over (comp, limb, group k); group k holds the images k + i h, i < g,
+// that exist (k + i h < B).  m: the factor's row per limb (one component, one
+// image), on the limbs of o / x.
+//
+// pack: o_k = sum_i M_i a_(k + i h), h = o.nbatch, B = a.nbatch
+__global__ void __launch_bounds__(256) mono_pack_kernel(LimbSet o, LimbSet a, LimbSet m, int g,
+                                                        const DeviceTables* __restrict__ tb, int N) {
+  const int row = blockIdx.y;
+  const int h = o.nbatch, B = a.nbatch;
+  const int k = row % h;
+  const int r = row / h;
+  const int l = r % o.nlimb;
+  const int c = r / o.nlimb;
+  const int n = (blockIdx.x * kBlk + threadIdx.x) * 2;
+  if (n >= N) return;
+  const ModConst mc = tb->mc[arg_byte(o.mod, l)];
+  const u64 q = mc.q;
+  ulonglong2 z = *(const ulonglong2*)(a.p + row_off(a, c, l, k) + n);
+  if (k + h < B && g > 1) {
+    const ulonglong2 w = *(const ulonglong2*)(m.p + row_off(m, 0, l, 0) + n);
+    ulonglong2 f = w;
+    for (int i = 1;;) {
+      const ulonglong2 x = *(const ulonglong2*)(a.p + row_off(a, c, l, k + i * h) + n);
+      z.x = add_mod(z.x, mul_mod(f.x, x.x, mc), q);
+      z.y = add_mod(z.y, mul_mod(f.y, x.y, mc), q);
+      if (++i >= g || k + i * h >= B) break;
+      f.x = mul_mod(f.x, w.x, mc);
+      f.y = mul_mod(f.y, w.y, mc);
+    }
+  }
+  *(ulonglong2*)(o.p + row_off(o, c, l, k) + n) = z;
+}
+
+// unpack: o_(k + i h) = M_-i x_k, h = x.nbatch, B = o.nbatch: each source row
+// is read once and its (at most g) images written
+__global__ void __launch_bounds__(256) mono_unpack_kernel(LimbSet o, LimbSet x, LimbSet m, int g,
+                                                          const DeviceTables* __restrict__ tb, int N) {
+  const int row = blockIdx.y;
+  const int h = x.nbatch, B = o.nbatch;
+  const int k = row % h;
+  const int r = row / h;
+  const int l = r % x.nlimb;
+  const int c = r / x.nlimb;
+  const int n = (blockIdx.x * kBlk + threadIdx.x) * 2;
+  if (n >= N) return;
+  const ModConst mc = tb->mc[arg_byte(x.mod, l)];
+  const ulonglong2 u = *(const ulonglong2*)(x.p + row_off(x, c, l, k) + n);
+  *(ulonglong2*)(o.p + row_off(o, c, l, k) + n) = u;
+  if (k + h < B && g > 1) {
+    const ulonglong2 w = *(const ulonglong2*)(m.p + row_off(m, 0, l, 0) + n);
+    ulonglong2 f = w;
+    for (int i = 1;;) {
+      *(ulonglong2*)(o.p + row_off(o, c, l, k + i * h) + n) =
+          make_ulonglong2(mul_mod(f.x, u.x, mc), mul_mod(f.y, u.y, mc));
+      if (++i >= g || k + i * h >= B) break;
+      f.x = mul_mod(f.x, w.x, mc);
+      f.y = mul_mod(f.y, w.y, mc);
+    }
+  }
+}
+
 // whole images gathered into a batch ciphertext: image i of the launch
 // (i < ORION_MAXGATHER) is copied from T.src[i] to dst + i*N, limb planes
 // (c, l), c < 2, l < nlimb, dst plane (c, l) at c*d_comp + l*d_limb.
@@ -1386,6 +1452,30 @@ int orion_launch_unpack_complex(const LimbSet& re, const LimbSet& im, const Limb
   Scalars sc;
   for (int l = 0; l < x.nlimb; ++l) sc.s[l] = w4[l], sc.ss[l] = w4s[l];
   hipLaunchKernelGGL(unpack_complex_kernel, ew_grid(N, rows), dim3(kBlk), 0, st, re, im, x, y, sc, nim, tb, N);
+  return 0;
+}
+
+// o_k = sum_i M_i a_(k + i h): o holds h = ceil(B / g) groups of a's B images; m1 = the row of M_1 per limb of o
+int orion_launch_mono_pack(const LimbSet& o, const LimbSet& a, const LimbSet& m1, int g, const DeviceTables* tb,
+                           int N, hipStream_t st) {
+  const int h = o.nbatch, B = a.nbatch;
+  const long long rows = (long long)o.ncomp * o.nlimb * h;
+  if (rows < 1 || rows > 65535 || N < 4 || (N & 3) || g < 1 || g > N || B < 1 || h != (B + g - 1) / g ||
+      a.ncomp != o.ncomp || a.nlimb != o.nlimb || m1.nlimb != o.nlimb || !o.p || !a.p || !m1.p)
+    return -1;
+  hipLaunchKernelGGL(mono_pack_kernel, ew_grid(N, (int)rows), dim3(kBlk), 0, st, o, a, m1, g, tb, N);
+  return 0;
+}
+
+// o_(k + i h) = M_-i x_k: x holds h = ceil(B / g) groups, o B images; mi = the row of M_-1 per limb of x
+int orion_launch_mono_unpack(const LimbSet& o, const LimbSet& x, const LimbSet& mi, int g, const DeviceTables* tb,
+                             int N, hipStream_t st) {
+  const int h = x.nbatch, B = o.nbatch;
+  const long long rows = (long long)x.ncomp * x.nlimb * h;
+  if (rows < 1 || rows > 65535 || N < 4 || (N & 3) || g < 1 || g > N || B < 1 || h != (B + g - 1) / g ||
+      o.ncomp != x.ncomp || o.nlimb != x.nlimb || mi.nlimb != x.nlimb || !o.p || !x.p || !mi.p)
+    return -1;
+  hipLaunchKernelGGL(mono_unpack_kernel, ew_grid(N, (int)rows), dim3(kBlk), 0, st, o, x, mi, g, tb, N);
   return 0;
 }
 

@@ -44,6 +44,10 @@ int orion_launch_pack_complex(const LimbSet& o, const LimbSet& a, const LimbSet&
                               const u64* w4s, const DeviceTables* tb, int N, hipStream_t st);
 int orion_launch_unpack_complex(const LimbSet& re, const LimbSet& im, const LimbSet& x, const LimbSet& y, int nim,
                                 const u64* w4, const u64* w4s, const DeviceTables* tb, int N, hipStream_t st);
+int orion_launch_mono_pack(const LimbSet& o, const LimbSet& a, const LimbSet& m1, int g, const DeviceTables* tb,
+                           int N, hipStream_t st);
+int orion_launch_mono_unpack(const LimbSet& o, const LimbSet& x, const LimbSet& mi, int g, const DeviceTables* tb,
+                             int N, hipStream_t st);
 int orion_launch_basis_ext(const LimbSet& out, const LimbSet& in, const BasisExtTable* T, const DeviceTables* tb,
                            int N, hipStream_t st);
 int orion_launch_basis_ext_rescale(const LimbSet& out, const LimbSet& in, const BextRescaleTable* W, int N,
